@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""bench.py -- headline benchmark (BASELINE.json): tips/sec FASTA -> Newick at N = 30k on MI355X, with the
-Q-argmin HBM roofline, the hot path's own kernel record, a self-check of the timed result and CPU NJ baselines
-timed on the host cores.
+"""bench.py -- headline benchmark (BASELINE.json): tips/sec FASTA -> Newick at N = 30k on MI355X; with --full also
+the Q-argmin HBM roofline, the hot path's own kernel record, a self-check of the timed result, CPU NJ baselines
+timed on the host cores, the other sizes and the multi-rank legs.
 
 One "step" = one pass of the whole path over one batch of synthetic input: the `dipper` command line (FASTA
 parse, pack, H2D, all-pairs JC69 distances, all N-2 NJ iterations, Newick write) on this rank's GPU.  `value`
-is BASELINE.json's metric measured over exactly K such steps.  The hot path alone (packed tips resident in HBM
--> distances -> NJ merge log, in process through the C ABI) is timed over the same K/W next to it (`hot_path`).
-Run as `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches it under
+is BASELINE.json's metric measured over exactly K such steps.  A plain run does nothing else: input, W warm-up
+steps, K timed steps, the outputs of the last step (--dump-outputs DIR) and the JSON line.  With --full the hot
+path alone (packed tips resident in HBM -> distances -> NJ merge log, in process through the C ABI) is timed over
+the same K/W next to it (`hot_path`), followed by everything listed above.
+Run as `python bench.py --gpus N --steps K --warmup W [--full]`; for N > 1 the driver launches it under
 torch.distributed.run (one rank per GPU, RCCL).  At 30 000 tips the default NJ (exact pruned scan) is ~16 us of
 dependent latency per iteration, which no exchange can shorten, so the headline steps are replicas (`scaling: weak`);
 north_star's own partitioning -- the matrix row-sharded over the ranks, one full Q scan per iteration -- is measured
@@ -23,6 +25,7 @@ import argparse
 import hashlib
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -139,6 +142,85 @@ def nrf_of(true_tree, newick_text_or_path, tmp, tag):
         return {"error": r.stderr[-200:]}
     d = json.loads(r.stdout)
     return {"nrf": d["nrf"], "rf": d["rf"], "splits_true": d["splits_a"], "splits_inferred": d["splits_b"]}
+
+
+# ---------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy (float64)
+# ---------------------------------------------------------------------------------------------------------
+DUMP_PAIRS = 1 << 19        # tip pairs whose path length is written: a fixed, seeded sample
+DUMP_SEED = 20240611
+
+
+def newick_arrays(text):
+    """(parent, length, {leaf name: node}) of a Newick text.  Nodes are numbered in the order they open, so a parent comes
+    before its children; the root's parent is -1, a missing length is 0.  Internal labels are ignored."""
+    parent, length, leaf = [], [], {}
+    stack, closed = [], None
+    for tok in re.split(r"([(),;])", text):
+        if tok == "(":
+            parent.append(stack[-1] if stack else -1)
+            length.append(0.0)
+            stack.append(len(parent) - 1)
+            closed = None
+        elif tok == ")":
+            closed = stack.pop()
+        elif tok in (",", ";"):
+            closed = None
+        elif tok.strip():
+            name, _, bl = tok.strip().partition(":")
+            if closed is None:          # a leaf
+                parent.append(stack[-1] if stack else -1)
+                length.append(0.0)
+                closed = len(parent) - 1
+                leaf[name] = closed
+            if bl:
+                length[closed] = float(bl)
+    return np.array(parent, dtype=np.int64), np.array(length, dtype=np.float64), leaf
+
+
+def tree_outputs(text, pairs=DUMP_PAIRS, seed=DUMP_SEED):
+    """The tree of a Newick text as arrays that do not depend on the order in which it lists children.  Tips are taken in
+    the order of their names by (length, text): T1, T2, ..., T10, ...  tip_branch_length / tip_root_distance: per tip;
+    tip_pair_index: a seeded sample of pairs of distinct tips; tip_pair_distance: the path length between them."""
+    parent, length, leaf = newick_arrays(text)
+    depth = np.zeros(len(parent))
+    level = np.zeros(len(parent), dtype=np.int64)
+    for v in range(1, len(parent)):
+        depth[v] = depth[parent[v]] + length[v]
+        level[v] = level[parent[v]] + 1
+    tips = np.array([leaf[k] for k in sorted(leaf, key=lambda s: (len(s), s))], dtype=np.int64)
+    n = len(tips)
+    p = min(pairs, n * (n - 1) // 2)
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, n, p)
+    b = rng.integers(0, max(n - 1, 1), p)
+    b += b >= a
+    # lowest common ancestors by binary lifting (ups[k] = the 2^k-th ancestor; the root is its own parent)
+    ups = [np.where(parent < 0, 0, parent)]
+    for _ in range(int(level.max(initial=0)).bit_length()):
+        ups.append(ups[-1][ups[-1]])
+    x, y = tips[a], tips[b]
+    swap = level[x] < level[y]
+    x, y = np.where(swap, y, x), np.where(swap, x, y)
+    diff = level[x] - level[y]
+    for k, up in enumerate(ups):
+        sel = ((diff >> k) & 1).astype(bool)
+        x[sel] = up[x[sel]]
+    for up in reversed(ups):
+        ux, uy = up[x], up[y]
+        ne = ux != uy
+        x, y = np.where(ne, ux, x), np.where(ne, uy, y)
+    lca = np.where(x == y, x, ups[0][x])
+    return {"tip_branch_length": length[tips], "tip_root_distance": depth[tips],
+            "tip_pair_index": np.stack([a, b], axis=1).astype(np.float64),
+            "tip_pair_distance": depth[tips[a]] + depth[tips[b]] - 2.0 * depth[lca]}
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step: {', '.join(sorted(arrays))} in {path}")
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -453,9 +535,19 @@ def main():
     ap.add_argument("--sharded-tips", type=int, default=100000)
     ap.add_argument("--sharded-sites", type=int, default=10000)
     ap.add_argument("--probe-only", action="store_true",
-                    help="skip the timed steps; only build the matrix and run the roofline probe "
+                    help="with --full: skip the timed steps; only build the matrix and run the roofline probe "
                          "(used for the rocprofv3 --pmc passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps: the hot path in process with its kernel record, the self-check of the timed "
+                         "result, the Q-argmin roofline, the CPU baselines, the other sizes and the multi-rank legs (the --no-* "
+                         "options choose among them).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64): for the `dipper` "
+                         "command the tree it wrote (per-tip branch lengths and root distances, path lengths of a seeded sample of "
+                         "tip pairs), for the in-process hot path the merge log")
     args = ap.parse_args()
+    if args.probe_only and not args.full:
+        ap.error("--probe-only is part of --full")
 
     # stdout carries exactly ONE line, the JSON record: everything else that writes to file descriptor 1 (RCCL prints
     # a version banner there when a communicator is created) is sent to stderr
@@ -537,6 +629,15 @@ def main():
     fa, nwk = inp["fasta"], os.path.join(tmp, "out.nwk")
     if args.probe_only:
         args.steps = args.warmup = 0
+    # the device the steps run on, opened through the library the `dipper` command links (set-up, before any timing): a
+    # device or a build of the library that cannot run the steps ends the run here, and the line names the device measured
+    ctx = dipper_amd.Dipper(local_rank)
+    try:
+        device = ctx.device_name()
+    finally:
+        ctx.close()
+    if rank == 0:
+        log(f"[bench] device {local_rank}: {device}")
 
     try:
         # =====================================================================================================
@@ -562,6 +663,9 @@ def main():
                 t = torch.tensor([dt_cli], dtype=torch.float64, device=TDEV)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 dt_cli = float(t.item())
+            if args.dump_outputs and rank == 0 and args.steps > 0:
+                with open(nwk) as f:
+                    dump_outputs(args.dump_outputs, tree_outputs(f.read()))
             others = [w - i - t for w, i, t in zip(walls, inputs, trees)]
             cli = {"metric": "tips/sec FASTA -> Newick, whole CLI run (process start, FASTA parse, pack, H2D, JC69 distances, NJ, Newick write)",
                    "command": "dipper -i m -I in.fa -O out.nwk -m 2 -d 2 --device <local rank>",
@@ -581,7 +685,7 @@ def main():
             # the same command with the GPU left alone for 0.4 s before every step: hip_startup_ms is then the process's OWN runtime
             # start-up (~105 ms), not the wait for its predecessor's teardown -- separates the command's cost from the artefact of
             # running steps back to back (round 5's verdict, item 8).  Untimed as far as `value` goes.
-            if rank == 0 and args.steps > 0 and budget.allows(12):
+            if args.full and rank == 0 and args.steps > 0 and budget.allows(12):
                 try:
                     iw, ii, it_, ir, ipar = [], [], [], [], []
                     for _ in range(min(args.steps, 5)):
@@ -597,118 +701,123 @@ def main():
 
         # =====================================================================================================
         # B. the hot path alone, in process through the C ABI: inputs resident in HBM -> distances -> NJ merge log
+        #    (--full; in a plain run only when it is the headline, i.e. without the command)
         # =====================================================================================================
-        dip = dipper_amd.Dipper(local_rank)
-        dip.set_nj_multi_plan(2)        # timed steps: every rank builds its own tree (no collective at 30k tips)
-        dip.set_msa(packed, L)          # H2D + bit-plane conversion: inputs now resident in HBM
-        if rank == 0:
-            log(f"[bench] device: {dip.device_name()}")
+        dip, hot, last_res, prune, nj_ms = None, None, None, None, []
+        if args.full or cli is None:
+            dip = dipper_amd.Dipper(local_rank)
+            dip.set_nj_multi_plan(2)        # timed steps: every rank builds its own tree (no collective at 30k tips)
+            dip.set_msa(packed, L)          # H2D + bit-plane conversion: inputs now resident in HBM
+            if rank == 0:
+                log(f"[bench] device: {dip.device_name()}")
 
-        def step():
-            dip.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
-            res = dip.nj_run()
-            assert res["iters"] == n - 2
-            return res
-
-        phase, walls_hp = [], []
-        prune = None
-        last_res = None
-        for _ in range(args.warmup):
-            step()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            ts = time.perf_counter()
-            last_res = step()
-            walls_hp.append((time.perf_counter() - ts) * 1e3)
-            phase.append(dip.timing())
-            try:
-                sc, full = dip.prune_stats()
-                prune = {"units_scanned": sc, "units_per_full_scan": full, "iterations": n - 2,
-                         "scanned_fraction_of_full_scans": sc / (full * (n - 2.0))}
-            except Exception:
-                prune = None
-        barrier()
-        dt_hp = time.perf_counter() - t0
-        if dist is not None:
-            t = torch.tensor([dt_hp], dtype=torch.float64, device=TDEV)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt_hp = float(t.item())
-        ms_hp = dt_hp / max(args.steps, 1) * 1e3 if args.steps else float("nan")
-        nj_ms = [p[1] for p in phase]
-        hot = {"metric": "tips/sec packed aligned tips resident in HBM -> JC69 distances -> NJ merge log (C ABI, in process)",
-               "value": world * n / (ms_hp * 1e-3) if args.steps else None, "unit": "tips/s", "ms_per_step": ms_hp,
-               "steps": args.steps, "warmup": args.warmup,
-               "step_ms": stats_ms(walls_hp),
-               "phase_ms": {"dist": stats_ms([p[0] for p in phase]), "nj": stats_ms(nj_ms)},
-               "nj_us_per_iteration": (float(np.median(nj_ms)) * 1e3 / (n - 2)) if nj_ms else None,
-               "nj_iterations_per_s": (world * (n - 2) / (float(np.median(nj_ms)) * 1e-3)) if nj_ms else None,
-               "nj_algorithm": "exact pruned scan (njp.hip)" if prune else "full streaming scan (nj.hip)",
-               "prune": prune}
-        log(f"[bench r{rank}] hot path steps: {hot['step_ms']} phases {hot['phase_ms']}")
-        if (args.model != "jc69" or not args.no_indel_gaps) and args.steps > 0 and not args.probe_only and n <= 50000:
-            # the same hot path on the input of rounds 1-3 (JC69 substitutions, no gaps), for comparison across rounds:
-            # one warm-up + two timed steps on a context of its own
-            try:
-                inp3 = stage.gen("main_r3", n, L, args.seed, 2e-5, 2e-6, 2e-4, gap=None, model="jc69")
-                d3 = dipper_amd.Dipper(local_rank)
-                try:
-                    d3.set_nj_multi_plan(2)
-                    d3.set_msa(Stage.packed4(inp3), L)
-                    ph3 = []
-                    for k in range(3):
-                        d3.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
-                        r3 = d3.nj_run()
-                        if k:
-                            ph3.append(d3.timing())
-                    hot["rounds_1_to_3_input"] = {"input": "jc69, no gaps", "dist_ms": float(np.mean([p[0] for p in ph3])),
-                                                  "nj_ms": float(np.mean([p[1] for p in ph3])), "units_scanned": d3.prune_stats()[0],
-                                                  "merge_log_digest": merge_digest(r3)}
-                finally:
-                    d3.close()
-            except Exception as e:
-                hot["rounds_1_to_3_input"] = {"error": repr(e)}
-
-        # ---- the timed kernels' own record: what the pruned scan read, and how fast ---------------------------
-        if prune and nj_ms and not args.probe_only:
-            try:
-                # one more NJ run, eager, HIP events on the library's stream around every 16th iteration's launches
-                dip.set_nj_kernel_timing(16)
+            def step():
                 dip.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
-                dip.nj_run()
-                kt = dip.nj_kernel_timing()
-            except Exception as e:
-                kt = {"error": repr(e)}
-            finally:
-                dip.set_nj_kernel_timing(0)
-            bytes_scanned = prune["units_scanned"] * float(UNIT_BYTES)
-            rec = {"kernels_per_iteration": kt.get("kernels_per_iteration"),
-                   "units_scanned_per_iteration": prune["units_scanned"] / (n - 2.0),
-                   "bytes_scanned_per_run_upper": bytes_scanned,
-                   "note": "bytes = listed units x 64 KiB (an upper bound: a listed unit's sub-units whose own bound rules "
-                           "them out are not loaded); kernel times: HIP events on the library's stream around every "
-                           "16th iteration's launches in one extra eager (not graph-replayed) run"}
-            rec.update({k: v for k, v in kt.items() if k != "kernels_per_iteration"})
-            if kt.get("scan_us_avg"):
-                # an event pair with nothing in between costs ~5 us on this stream: subtract it (the rocprofv3 averages of
-                # the same kernels, profiles/, are the reference these net figures have to agree with)
-                ev = kt.get("kernel_us_avg", {}).get("(empty event pair)", 0.0)
-                net = {k: max(v - ev, 0.0) for k, v in kt.get("kernel_us_avg", {}).items() if not k.startswith("(")}
-                rec["kernel_us_net_of_event_overhead"] = net
-                scan_net = max(kt["scan_us_avg"] - ev, 1e-3)
-                t_scan = scan_net * 1e-6 * (n - 2)
-                ach = bytes_scanned / t_scan / 1e9
-                rec["roofline_timed"] = {"bound": "latency (about 110 units = 7 MB per launch; HBM-bound only from ~100 000 tips on)",
-                                         "kernel": kt.get("scan_kernel"),
-                                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                                         "bytes_per_launch": bytes_scanned / (n - 2.0), "us_per_launch": scan_net}
-            hot["timed_kernels"] = rec
+                res = dip.nj_run()
+                assert res["iters"] == n - 2
+                return res
+
+            phase, walls_hp = [], []
+            prune = None
+            last_res = None
+            for _ in range(args.warmup):
+                step()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                ts = time.perf_counter()
+                last_res = step()
+                walls_hp.append((time.perf_counter() - ts) * 1e3)
+                phase.append(dip.timing())
+                try:
+                    sc, full = dip.prune_stats()
+                    prune = {"units_scanned": sc, "units_per_full_scan": full, "iterations": n - 2,
+                             "scanned_fraction_of_full_scans": sc / (full * (n - 2.0))}
+                except Exception:
+                    prune = None
+            barrier()
+            dt_hp = time.perf_counter() - t0
+            if dist is not None:
+                t = torch.tensor([dt_hp], dtype=torch.float64, device=TDEV)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt_hp = float(t.item())
+            ms_hp = dt_hp / max(args.steps, 1) * 1e3 if args.steps else float("nan")
+            nj_ms = [p[1] for p in phase]
+            hot = {"metric": "tips/sec packed aligned tips resident in HBM -> JC69 distances -> NJ merge log (C ABI, in process)",
+                   "value": world * n / (ms_hp * 1e-3) if args.steps else None, "unit": "tips/s", "ms_per_step": ms_hp,
+                   "steps": args.steps, "warmup": args.warmup,
+                   "step_ms": stats_ms(walls_hp),
+                   "phase_ms": {"dist": stats_ms([p[0] for p in phase]), "nj": stats_ms(nj_ms)},
+                   "nj_us_per_iteration": (float(np.median(nj_ms)) * 1e3 / (n - 2)) if nj_ms else None,
+                   "nj_iterations_per_s": (world * (n - 2) / (float(np.median(nj_ms)) * 1e-3)) if nj_ms else None,
+                   "nj_algorithm": "exact pruned scan (njp.hip)" if prune else "full streaming scan (nj.hip)",
+                   "prune": prune}
+            log(f"[bench r{rank}] hot path steps: {hot['step_ms']} phases {hot['phase_ms']}")
+            if args.dump_outputs and rank == 0 and cli is None and last_res is not None:
+                dump_outputs(args.dump_outputs, {k: last_res[k] for k in ("merge_x", "merge_y", "bl_x", "bl_y", "last_d")})
+            if args.full and (args.model != "jc69" or not args.no_indel_gaps) and args.steps > 0 and not args.probe_only and n <= 50000:
+                # the same hot path on the input of rounds 1-3 (JC69 substitutions, no gaps), for comparison across rounds:
+                # one warm-up + two timed steps on a context of its own
+                try:
+                    inp3 = stage.gen("main_r3", n, L, args.seed, 2e-5, 2e-6, 2e-4, gap=None, model="jc69")
+                    d3 = dipper_amd.Dipper(local_rank)
+                    try:
+                        d3.set_nj_multi_plan(2)
+                        d3.set_msa(Stage.packed4(inp3), L)
+                        ph3 = []
+                        for k in range(3):
+                            d3.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
+                            r3 = d3.nj_run()
+                            if k:
+                                ph3.append(d3.timing())
+                        hot["rounds_1_to_3_input"] = {"input": "jc69, no gaps", "dist_ms": float(np.mean([p[0] for p in ph3])),
+                                                      "nj_ms": float(np.mean([p[1] for p in ph3])), "units_scanned": d3.prune_stats()[0],
+                                                      "merge_log_digest": merge_digest(r3)}
+                    finally:
+                        d3.close()
+                except Exception as e:
+                    hot["rounds_1_to_3_input"] = {"error": repr(e)}
+
+            # ---- the timed kernels' own record: what the pruned scan read, and how fast ---------------------------
+            if args.full and prune and nj_ms and not args.probe_only:
+                try:
+                    # one more NJ run, eager, HIP events on the library's stream around every 16th iteration's launches
+                    dip.set_nj_kernel_timing(16)
+                    dip.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
+                    dip.nj_run()
+                    kt = dip.nj_kernel_timing()
+                except Exception as e:
+                    kt = {"error": repr(e)}
+                finally:
+                    dip.set_nj_kernel_timing(0)
+                bytes_scanned = prune["units_scanned"] * float(UNIT_BYTES)
+                rec = {"kernels_per_iteration": kt.get("kernels_per_iteration"),
+                       "units_scanned_per_iteration": prune["units_scanned"] / (n - 2.0),
+                       "bytes_scanned_per_run_upper": bytes_scanned,
+                       "note": "bytes = listed units x 64 KiB (an upper bound: a listed unit's sub-units whose own bound rules "
+                               "them out are not loaded); kernel times: HIP events on the library's stream around every "
+                               "16th iteration's launches in one extra eager (not graph-replayed) run"}
+                rec.update({k: v for k, v in kt.items() if k != "kernels_per_iteration"})
+                if kt.get("scan_us_avg"):
+                    # an event pair with nothing in between costs ~5 us on this stream: subtract it (the rocprofv3 averages of
+                    # the same kernels, profiles/, are the reference these net figures have to agree with)
+                    ev = kt.get("kernel_us_avg", {}).get("(empty event pair)", 0.0)
+                    net = {k: max(v - ev, 0.0) for k, v in kt.get("kernel_us_avg", {}).items() if not k.startswith("(")}
+                    rec["kernel_us_net_of_event_overhead"] = net
+                    scan_net = max(kt["scan_us_avg"] - ev, 1e-3)
+                    t_scan = scan_net * 1e-6 * (n - 2)
+                    ach = bytes_scanned / t_scan / 1e9
+                    rec["roofline_timed"] = {"bound": "latency (about 110 units = 7 MB per launch; HBM-bound only from ~100 000 tips on)",
+                                             "kernel": kt.get("scan_kernel"),
+                                             "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                                             "bytes_per_launch": bytes_scanned / (n - 2.0), "us_per_launch": scan_net}
+                hot["timed_kernels"] = rec
 
         # =====================================================================================================
         # C. self-check of the timed result (untimed)
         # =====================================================================================================
         parity = None
-        if last_res is not None and not args.no_parity and rank == 0:
+        if args.full and last_res is not None and not args.no_parity and rank == 0:
             parity = {"merge_log_digest": merge_digest(last_res)}
             try:
                 # (1) the streaming algorithm (the reference's: one full Q scan per iteration) on the bench's own input
@@ -765,8 +874,9 @@ def main():
 
         # ---- several ranks: same merge log everywhere (every rank built the same tree from the same input) ----
         mgpu_check = None
-        log(f"[bench r{rank}] +{elapsed():.0f}s: multi-rank digest check / roofline probe")
-        if dist is not None and last_res is not None:
+        if args.full:
+            log(f"[bench r{rank}] +{elapsed():.0f}s: multi-rank digest check / roofline probe")
+        if args.full and dist is not None and last_res is not None:
             digest = int(merge_digest(last_res)[:14], 16)
             mine = torch.tensor([digest], dtype=torch.int64, device=TDEV)
             allh = [torch.zeros_like(mine) for _ in range(world)]
@@ -776,15 +886,17 @@ def main():
         # =====================================================================================================
         # D. roofline of the Q-argmin (BASELINE metric 2): full streaming scan at n = N on a fresh matrix
         # =====================================================================================================
-        dip.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
-        _, _, _, scan_ms = dip.argmin_once(reps=args.probe_reps)
-        alg_bytes = 4.0 * n * n + 4.0 * n       # strict lower triangle + U once (this rank holds the whole matrix)
-        achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(n, 1),
-                    "kernel": "nj_scan_kernel<PROBE=true,...>: the full Q-argmin scan (SURVEY 8d's unit of work; the streaming NJ "
-                              "path runs it every iteration, the default pruned path does not -- see hot_path.timed_kernels)",
-                    "n_active": n, "algorithmic_bytes": alg_bytes, "ms": scan_ms}
+        roofline = None
+        if args.full:
+            dip.dist_matrix(capi.SRC_MSA, capi.DIST_JC)
+            _, _, _, scan_ms = dip.argmin_once(reps=args.probe_reps)
+            alg_bytes = 4.0 * n * n + 4.0 * n       # strict lower triangle + U once (this rank holds the whole matrix)
+            achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(n, 1),
+                        "kernel": "nj_scan_kernel<PROBE=true,...>: the full Q-argmin scan (SURVEY 8d's unit of work; the streaming NJ "
+                                  "path runs it every iteration, the default pruned path does not -- see hot_path.timed_kernels)",
+                        "n_active": n, "algorithmic_bytes": alg_bytes, "ms": scan_ms}
 
         primary = cli is not None
         ms_per_step = (dt_cli / max(args.steps, 1) * 1e3) if primary else ms_hp
@@ -802,7 +914,7 @@ def main():
                     % ("GTR+G4+I substitutions with the parameters of scripts/alisim.sh:21" if args.model == "gtr+g+i" else "JC69 substitutions", L, "no gaps" if args.no_indel_gaps else ("deletions of the authors' indel model as inherited gap runs (gen_synth --indel-gaps)"
                                                                  + ("; stress: + %.3g of every tip's cells as its own '-' runs" % args.gap_frac if args.gap_frac > 0 else ""))),
             "config": {"workload": "configs[1]: %d aligned tips, -d 2 (JC69), conventional NJ (-m 2)" % n,
-                       "tips": n, "sites": L,
+                       "tips": n, "sites": L, "device": device,
                        "step": "one whole `dipper` command per rank (FASTA -> Newick)" if primary else "in-process hot path (HBM-resident input -> merge log)",
                        "parallelism": "1 GPU" if world == 1 else
                                       ("replicas%d: every rank builds its own %d-tip tree on its own GPU, no collective "
@@ -812,19 +924,23 @@ def main():
             "e2e_cli": cli,
             "hot_path": hot,
             "phase_ms": {"dist": hot["phase_ms"]["dist"]["mean"] if hot["phase_ms"]["dist"] else None,
-                         "nj": hot["phase_ms"]["nj"]["mean"] if hot["phase_ms"]["nj"] else None},
+                         "nj": hot["phase_ms"]["nj"]["mean"] if hot["phase_ms"]["nj"] else None} if hot is not None else None,
             "roofline": roofline,
             "parity_check": parity,
             "input_staging": {"generated_once_by": "rank 0 (tools/bin/gen_synth, %d host threads)" % host_cores(), "seconds": dict(stage.times),
                               "directory": os.path.dirname(stage.dir), "host_threads_per_rank": threads},
         })
+        if not args.full:           # what a plain run did not measure is left out of its line
+            for k in ("hot_path", "phase_ms", "roofline", "parity_check"):
+                if out[k] is None:
+                    del out[k]
         if mgpu_check is not None:
             out["multi_gpu_check"] = mgpu_check
 
         # =====================================================================================================
         # E. CPU baselines (rank 0, one GPU): bounded samples on the GPU's own matrix
         # =====================================================================================================
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.probe_only:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.probe_only:
             cores = threads
             for key, fn, kw, need in (("cpu_baseline", cpu_baseline, {"cores": cores}, 35),
                                       ("cpu_baseline_1core", cpu_baseline, {"cores": 1, "budget_s": 10.0}, 25),
@@ -840,15 +956,17 @@ def main():
                 out["rapidnj_path_probe"] = rapidnj_probe(dip, n, cores, tmp)
             except Exception as e:
                 out["rapidnj_path_probe"] = {"found": None, "error": repr(e)}
-        dip.close()
-        dip = None
+        if dip is not None:
+            dip.close()
+            dip = None
 
         # =====================================================================================================
         # E2. north_star's partitioning on this run's GPUs: matrix row-sharded over the ranks, one full Q scan per
         #     iteration (streaming NJ) -- NJ iterations/s per exchange plan, next to one GPU alone and to the default plan
         # =====================================================================================================
-        log(f"[bench r{rank}] +{elapsed():.0f}s: nj_scaling")
-        if not args.probe_only and not args.no_stream_leg:
+        if args.full:
+            log(f"[bench r{rank}] +{elapsed():.0f}s: nj_scaling")
+        if args.full and not args.probe_only and not args.no_stream_leg:
             need = 25 + (0 if args.no_virtual_pruned else 45) + (12 * len(args.exchanges.split(",")) + 40 if world > 1 else 0)
             if budget.allows_all(need):
                 try:
@@ -864,7 +982,7 @@ def main():
         #     the buffers is inside the figures): NJ at 100 000 tips, k-closest placement of 100 000 unaligned tips (Mash),
         #     divide-and-conquer of 1 000 000 aligned tips
         # =====================================================================================================
-        if world == 1 and rank == 0 and not args.no_other_configs and not args.probe_only:
+        if args.full and world == 1 and rank == 0 and not args.no_other_configs and not args.probe_only:
             try:
                 out["other_configs"] = other_configs(args, local_rank, stage, budget, tmp)
             except Exception as e:
@@ -873,15 +991,16 @@ def main():
         # =====================================================================================================
         # F. several GPUs: 100 000 tips (80 GB matrix): unit-sharded pruned plan, row-sharded streaming plans, DC of 1 M tips
         # =====================================================================================================
-        log(f"[bench r{rank}] +{elapsed():.0f}s: other sizes")
+        if args.full:
+            log(f"[bench r{rank}] +{elapsed():.0f}s: other sizes")
         run_sharded = world > 1 or force_check
-        if run_sharded and not args.no_sharded and not args.probe_only:
+        if args.full and run_sharded and not args.no_sharded and not args.probe_only:
             try:
                 out["sharded_100k"] = sharded_leg(args, rank, world, local_rank, dist, torch, barrier, stage, budget)
             except Exception as e:
                 out["sharded_100k"] = {"error": repr(e)}
         # F2. the product's own multi-GPU boundary: the `dipper` command with one rank per GPU (configs[1]-[4]) next to one GPU
-        if run_sharded and not args.probe_only and not args.no_cli and os.path.exists(EXE):
+        if args.full and run_sharded and not args.probe_only and not args.no_cli and os.path.exists(EXE):
             try:
                 out["cli_ranks"] = cli_ranks_leg(args, rank, world, local_rank, dist if world > 1 else None, stage, budget, tmp, fa if want_cli else None)
             except Exception as e:

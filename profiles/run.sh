@@ -3,7 +3,7 @@
 # produced by one of these steps (profiles/r<round>/README.md maps record -> step).  Steps are joined with && inside one gpurun call:
 #   bash profiles/run.sh suite                     whole `-m gpu` suite as the driver runs it, then smoke()
 #   bash profiles/run.sh tests <tag> <pytest args> a subset, first failure lines printed, non-zero exit on failure
-#   bash profiles/run.sh bench <tag> [bench args]  bench.py, its JSON line kept, headline fields printed
+#   bash profiles/run.sh bench <tag> [bench args]  bench.py --full, its JSON line kept, headline fields printed
 #   bash profiles/run.sh variants <tag> "<nj_target.py args>" [VAR=VALUE|-]...   NJ timing per env variant ("-" = none)
 #   bash profiles/run.sh rehearse                  bench.py's multi-rank control flow on ONE GPU (1 rank RCCL; 2 process ranks)
 #   bash profiles/run.sh hiptrace <tag>            HIP API trace of one `dipper` command (30 000 x 10 000)
@@ -28,7 +28,7 @@ tests)
     ;;
 bench)
     TAG=$1; shift; O=gpurun_out/${DPR_ROUND:-r5}/$TAG; mkdir -p $O
-    ( time python bench.py "$@" > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; rc=$?
+    ( time python bench.py --full "$@" > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt; rc=$?
     echo "bench rc=$rc"; tail -3 $O/bench_time.txt
     [ $rc -eq 0 ] || { tail -5 $O/bench.err; exit 1; }
     python3 - <<PY
@@ -55,9 +55,9 @@ variants)
 rehearse)
     O=gpurun_out/${DPR_ROUND:-r5}/rehearse; mkdir -p $O
     export HSA_ENABLE_IPC_MODE_LEGACY=0
-    DPR_BENCH_CHECK=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 2 --warmup 1 > $O/bench_check_one_rank_rccl.json 2> $O/a.err; rc=$?
+    DPR_BENCH_CHECK=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 2 --warmup 1 --full > $O/bench_check_one_rank_rccl.json 2> $O/a.err; rc=$?
     echo "one rank, RCCL, cross-checks on: rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/a.err; exit 1; }
-    DPR_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_2proc_one_gpu.json 2> $O/b.err; rc=$?
+    DPR_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 2 --warmup 1 --full > $O/bench_2proc_one_gpu.json 2> $O/b.err; rc=$?
     echo "two process ranks on one GPU: rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/b.err; exit 1; }
     python3 - <<PY
 import json

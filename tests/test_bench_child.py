@@ -83,3 +83,31 @@ def test_cli_phase_lines_are_parsed():
             "Device ready in: 111 ms\nSketch Created in: 38 ms\nDistance Operation Time 3640 ms\nTree Operation Time 2269 ms\n"
             "Distance batches overlapped with tree operations: 0 of 49, 0 ms in flight\nTree Created in: 557 ms\n")
     assert bench.cli_phases(text) == {"input_ms": 132.0, "device_ready_ms": 111.0, "sketch_ms": 38.0, "distance_ms": 3640.0, "tree_op_ms": 2269.0, "tree_ms": 557.0}
+
+
+def test_dumped_tree_arrays_are_path_lengths():
+    """--dump-outputs writes the command's tree as per-tip arrays and path lengths of seeded tip pairs: they equal the patristic
+    distances of the Newick text and do not change when the text lists the children of a node in the other order"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from tests import _util
+    rng = np.random.default_rng(5)
+    n = 60
+    mx, my = np.zeros(n - 2, np.int32), np.zeros(n - 2, np.int32)
+    for it in range(n - 2):
+        mx[it], my[it] = rng.choice(n - it, 2, replace=False)
+    bx, by = rng.exponential(0.01, n - 2), rng.exponential(0.01, n - 2)
+    names = ["T%d" % (i + 1) for i in range(n)]
+    text = _util.newick_from_merges(names, mx, my, bx, by, 0.05)
+    out = bench.tree_outputs(text)
+    assert set(out) == {"tip_branch_length", "tip_root_distance", "tip_pair_index", "tip_pair_distance"}
+    ij = out["tip_pair_index"].astype(np.int64)
+    assert len(ij) == n * (n - 1) // 2 and np.all(ij[:, 0] != ij[:, 1])
+    D = _util.patristic(text, names)
+    assert np.allclose(out["tip_pair_distance"], D[ij[:, 0], ij[:, 1]], rtol=1e-12, atol=0)
+    a = bench.tree_outputs("((T1:0.1,T2:0.2):0.3,(T3:0.4,(T4:0.5,T5:0.6):0.7):0.8);\n")
+    b = bench.tree_outputs("(((T5:0.6,T4:0.5):0.7,T3:0.4):0.8,(T2:0.2,T1:0.1):0.3);\n")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.allclose(a["tip_root_distance"], [0.4, 0.5, 1.2, 2.0, 2.1])
