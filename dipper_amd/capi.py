@@ -133,6 +133,11 @@ def load_library():
     L.dpr_dc_query_share.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dpr_dc_deal_clusters.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int, c_i32p]
     L.dpr_get_dc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), c_f64p]
+    L.dpr_msa_resample.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
+    L.dpr_get_msa_boot_weights.argtypes = [C.c_void_p, c_i32p]
+    L.dpr_msa_boot_weights.argtypes = [C.c_uint64, C.c_int64, C.c_int64, c_i32p]
+    L.dpr_split_support.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]
+    L.dpr_comm_sum_i32.argtypes = [C.c_void_p, c_i32p, C.c_int64]
     _LIB = L
     return L
 
@@ -228,6 +233,26 @@ def pack2(seq: bytes):
     out = np.zeros((len(seq) + 31) // 32, dtype=np.uint64)
     _chk(L, L.dpr_pack2(seq, len(seq), _p(out, c_u64p)))
     return out
+
+
+def msa_boot_weights(seed, replicate, L):
+    """multiplicity of every column of an L-site alignment in bootstrap replicate `replicate` (host only)"""
+    lib = load_library()
+    out = np.zeros(L, dtype=np.int32)
+    _chk(lib, lib.dpr_msa_boot_weights(seed, replicate, L, _p(out, c_i32p)))
+    return out
+
+
+def split_support(n, main_x, main_y, rep_x, rep_y, counts=None):
+    """counts[k] (internal node n+k of the main merge log) + 1 where the replicate's merge log has that node's split (host only)"""
+    lib = load_library()
+    k = max(n - 2, 1)
+    mx, my, rx, ry = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)[: n - 2]) for a in (main_x, main_y, rep_x, rep_y))
+    if counts is None:
+        counts = np.zeros(k, dtype=np.int32)
+    assert counts.dtype == np.int32 and counts.flags.c_contiguous and len(counts) >= n - 2
+    _chk(lib, lib.dpr_split_support(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), _p(counts, c_i32p)))
+    return counts
 
 
 def pack4_many(seqs):
@@ -609,6 +634,22 @@ class Dipper:
         _chk(self.L, self.L.dpr_msa_dist_block(self.h, row0, nrows, ncols, dist_type, 1 if transposed else 0,
                                                _p(out, c_f64p) if fetch else None, reps, C.byref(ms)))
         return out, ms.value
+
+    def msa_resample(self, seed, replicate):
+        """the MSA planes become those of bootstrap replicate `replicate` (-1: the uploaded alignment again)"""
+        _chk(self.L, self.L.dpr_msa_resample(self.h, seed, replicate))
+
+    def msa_boot_weights(self, L):
+        """the active replicate's column multiplicities as the device computed them"""
+        out = np.zeros(L, dtype=np.int32)
+        _chk(self.L, self.L.dpr_get_msa_boot_weights(self.h, _p(out, c_i32p)))
+        return out
+
+    def comm_sum_i32(self, values):
+        """in-place integer sum over the context's ranks"""
+        a = np.ascontiguousarray(values, dtype=np.int32)
+        _chk(self.L, self.L.dpr_comm_sum_i32(self.h, _p(a, c_i32p), len(a)))
+        return a
 
     def msa_counts(self, row):
         u = np.zeros(max(row, 1), dtype=np.int32)

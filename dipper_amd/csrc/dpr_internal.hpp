@@ -65,6 +65,22 @@ __host__ __device__ inline uint64_t nj_key_b(int64_t j)  // part depending on "j
     return ((uint64_t)(j & 255) << 48) | ((uint64_t)j << 24);
 }
 
+// ---- bootstrap column sample (boot.hip; dpr_msa_boot_weights restates it on the host from the same functions) -------------
+// splitmix64's finaliser.  Replicate r of an alignment of L sites (L < 2^32) draws column_t = ((mix64(key_r ^ t) >> 32) * L) >> 32,
+// t = 0 .. L-1, key_r = mix64(seed ^ mix64(r)); uint64 arithmetic, wrapping.
+__host__ __device__ inline uint64_t mix64(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__host__ __device__ inline uint64_t boot_key(uint64_t seed, int64_t replicate) { return mix64(seed ^ mix64((uint64_t)replicate)); }
+__host__ __device__ inline int64_t boot_column(uint64_t key, int64_t t, int64_t L)
+{
+    return (int64_t)(((mix64(key ^ (uint64_t)t) >> 32) * (uint64_t)L) >> 32);
+}
+
 struct alignas(32) NjRecord {
     double q;
     uint64_t key;
@@ -366,11 +382,23 @@ struct MsaBuffers {
     double* jc_tab = nullptr;    // [2][(L + 1) * (L + 1)]; longer alignments: the band [2][kMsaBand + 1][L + 1] (useful = L - g)
     // per sequence: bit j = its 16-word stage j holds a not-a-base position (gap, N, padding); stages from 63 on share bit 63
     unsigned long long* xstage = nullptr;
+    // bootstrap replicates (boot.hip): planes / xstage above are the ACTIVE alignment's; alt_* is the other set -- the
+    // replicate buffers while the uploaded alignment is active, the uploaded alignment's while a replicate is (a replicate
+    // has the same L, so jc_tab serves both)
+    uint32_t* alt_planes = nullptr;
+    unsigned long long* alt_xstage = nullptr;
+    int32_t* boot_w = nullptr;      // [L] multiplicity of every column in the active replicate
+    uint32_t* boot_incl = nullptr;  // [L] inclusive scan of boot_w
+    int32_t* boot_src = nullptr;    // [32 W32] source column of every replicate position, -1 = padding
+    int64_t replicate = -1;         // active replicate, -1 = the uploaded alignment
 };
 constexpr int64_t kMsaTabSites = 1024;
 constexpr int kMsaBand = 15;
 int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hipStream_t s);
 void msa_free(MsaBuffers& m);
+int msa_restage(MsaBuffers& m, hipStream_t s);     // m.xstage of the active planes again (nothing to do without xstage)
+// mash_index.hip: out[i] = in[0] + ... + in[i] (in and out must not alias); synchronises s
+int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s);
 int msa_dist_rows(const MsaBuffers& m, NjBuffers& b, int dist_type, hipStream_t s);
 int msa_dist_tile_edge(int dist_type);   // rows/columns per job tile of msa_dist_jobs
 int msa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s);

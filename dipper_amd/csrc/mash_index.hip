@@ -201,7 +201,8 @@ __global__ __launch_bounds__(kIThreads) void mi_scan_apply_kernel(const uint32_t
     }
 }
 // out[i] = in[0] + ... + in[i]; in and out may be the same buffer only if ... they must not alias
-static int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s)
+// (also the bootstrap's column scan, boot.hip)
+int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s)
 {
     if (n <= 0) return DPR_OK;
     const int64_t per = (int64_t)kIThreads * kScanItems;

@@ -663,7 +663,20 @@ void msa_free(MsaBuffers& m)
     if (m.planes) (void)hipFree(m.planes);
     if (m.jc_tab) (void)hipFree(m.jc_tab);
     if (m.xstage) (void)hipFree(m.xstage);
+    if (m.alt_planes) (void)hipFree(m.alt_planes);
+    if (m.alt_xstage) (void)hipFree(m.alt_xstage);
+    if (m.boot_w) (void)hipFree(m.boot_w);
+    if (m.boot_incl) (void)hipFree(m.boot_incl);
+    if (m.boot_src) (void)hipFree(m.boot_src);
     m = MsaBuffers();
+}
+
+int msa_restage(MsaBuffers& m, hipStream_t s)
+{
+    if (!m.xstage) return DPR_OK;
+    hipLaunchKernelGGL(msa_xstage_kernel, dim3((unsigned)((m.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, m.n, m.W32, m.L, m.xstage);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
 }
 
 int msa_dist_rows(const MsaBuffers& m, NjBuffers& b, int dist_type, hipStream_t s)

@@ -244,9 +244,26 @@ inline bool cliLog()
     return s.find(",cli,") != std::string::npos || s.find(",cli=") != std::string::npos;
 }
 
-// Newick text of an NJ merge log (bookkeeping + print of src/neighborJoining.cu:233-270), iterative.
+// Newick text of an NJ merge log (bookkeeping + print of src/neighborJoining.cu:233-270), iterative.  labels (optional, N-2
+// entries): (*labels)[k] >= 0 is written after the `)` of internal node N+k (bootstrap support); without labels the text is
+// the reference's.
 void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
                            const std::vector<int32_t>& my, const std::vector<double>& bx,
-                           const std::vector<double>& by, double last_d);
+                           const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels = nullptr);
+
+// ---- bootstrap support (support.cpp; no reference counterpart) -----------------------------------------------------------
+struct BootstrapOptions {
+    int64_t replicates = 0;      // --bootstrap N (0 = off)
+    uint64_t seed = 1;           // --bootstrap-seed S
+};
+// Support labels of the main tree (merge log mx / my of n tips) from summed counts over `replicates` replicates: the integer
+// percentage, rounded half up, for internal nodes with a non-trivial split, -1 elsewhere.
+std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
+                                   const std::vector<int32_t>& counts, int64_t replicates);
+// The NJ tree of -i m -o t with --bootstrap: the main tree exactly as findNeighbourJoiningTree builds it, then this rank's
+// replicates (r mod world == rank) on `dev` (one rank) or on a rank-local second context over `packed4` (several ranks), one
+// integer sum of the split counts over the ranks, and the labelled Newick.
+void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& params, const BootstrapOptions& bo,
+                                   const uint64_t* packed4, int seqLen, std::vector<std::string>& name, std::ostream& output_);
 
 }  // namespace dipper

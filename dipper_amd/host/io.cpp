@@ -619,9 +619,18 @@ void MatrixReader::read(const std::string& path)
 
 void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
                            const std::vector<int32_t>& my, const std::vector<double>& bx,
-                           const std::vector<double>& by, double last_d)
+                           const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels)
 {
     const int N = (int)name.size();
+    // the `)` that closes internal node `node` (never the root: its `)` is followed by ';')
+    auto close = [&](TextBuf& out, int node) {
+        out.put(')');
+        if (labels && node >= N && node < 2 * N - 2 && (*labels)[(size_t)(node - N)] >= 0) {
+            char b[16];
+            const auto r = std::to_chars(b, b + sizeof b, (*labels)[(size_t)(node - N)]);
+            out.s.append(b, (size_t)(r.ptr - b));
+        }
+    };
     struct Child { int node; double len; };
     std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });  // two children per internal node
     std::vector<int> realID((size_t)N);
@@ -651,7 +660,8 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
             if (st.empty()) break;
             Frame& up = st.back();
             const Child& c = kids[(size_t)up.node * 2 + (size_t)(up.next - 1)];
-            out.put(':'); out.putLength(c.len); out.put(up.next == 2 ? ')' : ',');
+            out.put(':'); out.putLength(c.len);
+            if (up.next == 2) close(out, up.node); else out.put(',');
             continue;
         }
         const Child& c = kids[(size_t)f.node * 2 + (size_t)f.next];
@@ -660,7 +670,8 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
             out.put('(');
             st.push_back(Frame{ c.node, 0 });
         } else {
-            out.put(name[(size_t)c.node]); out.put(':'); out.putLength(c.len); out.put(f.next == 2 ? ')' : ',');
+            out.put(name[(size_t)c.node]); out.put(':'); out.putLength(c.len);
+            if (f.next == 2) close(out, f.node); else out.put(',');
         }
     }
     out.put(";\n");

@@ -9,6 +9,7 @@
 
 #include <unistd.h>
 
+#include <cctype>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -67,7 +68,12 @@ static const char* kHelp =
     "  --transport arg             auto (default) | rccl | ipc: how the ranks exchange data\n"
     "  --rank arg --world arg --rendezvous arg\n"
     "                              this process is rank `rank` of `world` ranks started from outside;\n"
-    "                              they meet in the POSIX shared memory object `rendezvous`\n";
+    "                              they meet in the POSIX shared memory object `rendezvous`\n"
+    "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
+    "                              with replacement); the NJ tree's internal nodes are labelled with\n"
+    "                              the percentage of replicate trees that hold their split.\n"
+    "                              -i m -o t with conventional NJ only (-m 2, or -m 0 below 30000)\n"
+    "  --bootstrap-seed arg        Seed of the replicates' column draws (unsigned 64-bit, default 1)\n";
 
 struct Opt { const char* lng; char sht; bool has_arg; };
 static const Opt kOpts[] = {
@@ -77,6 +83,7 @@ static const Opt kOpts[] = {
     { "add", 'a', false }, { "input-tree", 't', true }, { "help", 'h', false },
     { "seed", 0, true }, { "device", 0, true }, { "gpus", 0, true }, { "devices", 0, true }, { "transport", 0, true },
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true },
+    { "bootstrap", 0, true }, { "bootstrap-seed", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -221,6 +228,34 @@ int main(int argc, char** argv)
         if (!vm.count(req)) usageError(std::string("the option '--") + req + "' is required but missing");
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
+    // --bootstrap: what the arguments alone decide is checked here, before any input is read or a GPU touched
+    BootstrapOptions boot;
+    if (vm.count("bootstrap-seed") && !vm.count("bootstrap")) usageError("--bootstrap-seed needs --bootstrap");
+    if (vm.count("bootstrap")) {
+        auto whole = [](const std::string& v, bool sign_ok) {
+            if (v.empty() || v.size() > 20) return false;
+            for (size_t i = 0; i < v.size(); ++i)
+                if (!std::isdigit((unsigned char)v[i]) && !(sign_ok && i == 0 && (v[i] == '-' || v[i] == '+') && v.size() > 1)) return false;
+            return true;
+        };
+        const std::string nv = vm["bootstrap"];
+        long long nr = 0;
+        try { nr = whole(nv, true) ? std::stoll(nv) : 0; } catch (...) { nr = 0; }
+        if (nr <= 0 || nr > (1ll << 30)) usageError("--bootstrap: the number of replicates must be a whole number >= 1");
+        boot.replicates = nr;
+        if (vm.count("bootstrap-seed")) {
+            const std::string sv = vm["bootstrap-seed"];
+            try {
+                if (!whole(sv, false)) throw 0;
+                boot.seed = (uint64_t)std::stoull(sv);
+            } catch (...) { usageError("--bootstrap-seed: an unsigned 64-bit integer"); }
+        }
+        const std::string in = strOr(vm, "input-format", "r"), out = strOr(vm, "output-format", "t"), al = strOr(vm, "algorithm", "0");
+        if (in != "m") usageError("--bootstrap needs aligned sequences (-i m)");
+        if (vm.count("add")) usageError("--bootstrap is not supported with --add");
+        if (out != "t") usageError("--bootstrap needs tree output (-o t)");
+        if (al == "1" || al == "3") usageError("--bootstrap needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+    }
 
     Param params;
     params.kmerSize = stoiOr(vm, "kmer-size", 15);
@@ -477,6 +512,9 @@ int main(int argc, char** argv)
         }
         const size_t numSequences = packed.ok ? packed.numSequences : seqs.size();
         if (numSequences < 3) die("ERROR: need at least three sequences in " + inputFile);
+        if (boot.replicates > 0 && pick_mode((long long)numSequences) != 2)
+            die("ERROR: --bootstrap needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (multi) { startRanks(ranks, device); adev.reset(new AsyncDeviceContext(rankInfo().device)); }
         auto output_ = open_out();
         DeviceContext& dev = adev->get();
@@ -538,7 +576,16 @@ int main(int argc, char** argv)
             NJDeviceArrays njDeviceArrays;
             njDeviceArrays.getDismatrix(dev, (int)numSequences, params, nullptr);
             if (cliLog()) std::cerr << "  getDismatrix call " << ms_since(t0) << " ms\n";
-            njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
+            if (boot.replicates > 0) {
+                // (several ranks: a rank-local context needs the packed alignment; FASTQ input is packed here once more)
+                std::vector<uint64_t> flat;
+                int seqLen = msaDeviceArrays.seqLen;
+                if (!packed.ok && rankInfo().world > 1) packAligned(seqs, ids, flat, seqLen);
+                bootstrapNeighbourJoiningTree(dev, (int)numSequences, params, boot, packed.ok ? packed.flat.data() : flat.data(),
+                                              seqLen, names, *output_);
+            } else {
+                njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
+            }
             std::cerr << "Tree Created in: " << ms_since(t0) << " ms\n";
         }
         printRankSummary(dev.ctx);

@@ -1,0 +1,105 @@
+// Bootstrap support of the NJ tree of aligned sequences (`--bootstrap N`; no reference counterpart).
+//
+// The main tree is built exactly as without the option.  Then every rank runs its replicates r = rank, rank + world, .. with
+// no collective: dpr_msa_resample (replicate alignment, on the device) -> dpr_dist_matrix -> dpr_nj_run -> dpr_split_support
+// (host) into per-node counts.  One rank: the replicates reuse the main context and its NJ buffers.  Several ranks: each runs
+// them on a rank-local second context on its own device (one rank, so no plan of the joined context -- and no collective --
+// reaches the replicate loop).  One integer sum over the ranks combines the counts; rank 0 writes the labelled Newick.
+#include "dipper_host.hpp"
+
+#include <chrono>
+#include <iostream>
+
+namespace dipper {
+
+std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
+                                   const std::vector<int32_t>& counts, int64_t replicates)
+{
+    std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
+    if (n <= 3 || replicates <= 0) return labels;
+    // clade sizes with the realID bookkeeping of writeNewickFromMerges
+    std::vector<int64_t> size((size_t)(2 * n - 2), 1);
+    std::vector<int32_t> real((size_t)n);
+    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
+    for (int64_t it = 0; it < n - 2; ++it) {
+        const int32_t x = mx[(size_t)it], y = my[(size_t)it];
+        size[(size_t)(n + it)] = size[(size_t)real[(size_t)x]] + size[(size_t)real[(size_t)y]];
+        real[(size_t)x] = (int32_t)(n + it);
+        real[(size_t)y] = real[(size_t)(n - it - 1)];
+    }
+    for (int64_t k = 0; k < n - 2; ++k) {
+        const int64_t s = size[(size_t)(n + k)];
+        if (s >= 2 && s <= n - 2) labels[(size_t)k] = (int32_t)((200 * (int64_t)counts[(size_t)k] + replicates) / (2 * replicates));
+    }
+    return labels;
+}
+
+void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& params, const BootstrapOptions& bo,
+                                   const uint64_t* packed4, int seqLen, std::vector<std::string>& name, std::ostream& output_)
+{
+    using Clock = std::chrono::steady_clock;
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const int64_t n = numSequences, k = std::max<int64_t>(n - 2, 1);
+    const RankInfo& ri = rankInfo();
+    // the main tree (findNeighbourJoiningTree's run); its merge log is kept
+    std::vector<int32_t> mx((size_t)k), my((size_t)k);
+    std::vector<double> bx((size_t)k), by((size_t)k);
+    double last = 0.0;
+    const int64_t done = dpr_nj_run(dev.ctx, -1, mx.data(), my.data(), bx.data(), by.data(), &last);
+    if (done < 0) gpuCheck((int)done, "dpr_nj_run");
+    if (cliLog()) {
+        double dist_ms = 0, nj_ms = 0;
+        dpr_get_timing(dev.ctx, &dist_ms, &nj_ms);
+        std::cerr << "  main tree: device distances " << dist_ms << " ms, NJ " << nj_ms << " ms\n";
+    }
+
+    const auto tb0 = Clock::now();
+    std::vector<int32_t> counts((size_t)k, 0);
+    dpr_ctx* rctx = dev.ctx;
+    auto fail = [&](int64_t r, const char* what, int rc) {
+        die("ERROR: bootstrap replicate " + std::to_string(r) + ": " + what + " failed (" + std::to_string(rc) + "): " + dpr_last_error());
+    };
+    if (ri.world > 1 && ri.rank < bo.replicates) {
+        // rank-local context: one rank, its own matrix (a second n x n on this device)
+        dpr_ctx* c = nullptr;
+        if (int rc = dpr_create(&c, ri.device)) fail(ri.rank, "dpr_create (rank-local context)", rc);
+        rctx = c;
+        if (int rc = dpr_set_msa(rctx, packed4, n, seqLen)) fail(ri.rank, "dpr_set_msa (rank-local context)", rc);
+    }
+    std::vector<int32_t> rx((size_t)k), ry((size_t)k);
+    std::vector<double> rbx((size_t)k), rby((size_t)k);
+    int64_t mine = 0;
+    double mine_ms = 0;
+    for (int64_t r = ri.rank; r < bo.replicates; r += ri.world) {
+        const auto t0 = Clock::now();
+        if (int rc = dpr_msa_resample(rctx, bo.seed, r)) fail(r, "dpr_msa_resample", rc);
+        const auto t1 = Clock::now();
+        if (int rc = dpr_dist_matrix(rctx, DPR_SRC_MSA, (int)params.distanceType, 0)) fail(r, "dpr_dist_matrix", rc);
+        const auto t2 = Clock::now();
+        double rlast = 0.0;
+        const int64_t rdone = dpr_nj_run(rctx, -1, rx.data(), ry.data(), rbx.data(), rby.data(), &rlast);
+        if (rdone < 0) fail(r, "dpr_nj_run", (int)rdone);
+        const auto t3 = Clock::now();
+        if (int rc = dpr_split_support(n, mx.data(), my.data(), rx.data(), ry.data(), counts.data())) fail(r, "dpr_split_support", rc);
+        const auto t4 = Clock::now();
+        ++mine;
+        mine_ms += ms(t0, t4);
+        if (cliLog()) {
+            double dist_ms = 0, nj_ms = 0;
+            dpr_get_timing(rctx, &dist_ms, &nj_ms);
+            std::cerr << "  replicate " << r << ": resample " << ms(t0, t1) << " ms, distances " << ms(t1, t2) << " ms (device "
+                      << dist_ms << "), NJ " << ms(t2, t3) << " ms (device " << nj_ms << "), split count " << ms(t3, t4) << " ms\n";
+        }
+    }
+    if (rctx != dev.ctx) dpr_destroy(rctx);
+    else gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, -1), "dpr_msa_resample");
+    if (n > 2) gpuCheck(dpr_comm_sum_i32(dev.ctx, counts.data(), n - 2), "dpr_comm_sum_i32");
+    const auto tb1 = Clock::now();
+
+    const std::vector<int32_t> labels = supportLabels(n, mx, my, counts, bo.replicates);
+    writeNewickFromMerges(output_, name, mx, my, bx, by, last, &labels);
+    std::cerr << "Bootstrap: " << bo.replicates << " replicates (seed " << bo.seed << ") in " << (long long)ms(tb0, tb1) << " ms, "
+              << (mine ? mine_ms / (double)mine : 0.0) << " ms per replicate, " << ri.world << " ranks\n";
+}
+
+}  // namespace dipper

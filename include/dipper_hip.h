@@ -378,6 +378,30 @@ int dpr_dc_deal_clusters(const int64_t *sizes_desc, int64_t count, int world, in
  * phase_ms: backbone tree, cluster assignment, cluster trees (HIP events) */
 int dpr_get_dc_stats(dpr_ctx *ctx, int64_t *counts5, double *phase_ms3);
 
+/* ---- bootstrap support of NJ trees from aligned sequences (no reference counterpart) ---------------------------------------
+ * Replicate r (0-based) of an alignment of L sites draws L columns with replacement (uint64 arithmetic, wrapping):
+ *   mix64(z) = splitmix64's finaliser; key_r = mix64(seed ^ mix64(r)); column_t = ((mix64(key_r ^ t) >> 32) * L) >> 32,
+ *   t = 0 .. L-1; w[c] = #{t : column_t = c}.
+ * The replicate alignment is every column c, ascending, repeated w[c] times.  It depends on (seed, r, L) only. */
+/* The context's MSA planes become those of replicate `replicate` (>= 0) -- on the device; the uploaded planes stay there --
+ * or those of the uploaded alignment again (-1).  Takes effect for dpr_dist_matrix, dpr_msa_dist_block and
+ * dpr_get_msa_counts, whose results are then bit for bit those of dpr_set_msa with the replicate alignment.
+ * DPR_ERR_STATE without dpr_set_msa; a later dpr_set_msa drops the replicate. */
+int dpr_msa_resample(dpr_ctx *ctx, uint64_t seed, int64_t replicate);
+/* test hook: w[] of the active replicate as the device computed it (L entries); DPR_ERR_STATE when none is active */
+int dpr_get_msa_boot_weights(dpr_ctx *ctx, int32_t *out);
+/* host only, no GPU: w[] of replicate `replicate` (L entries), from the same mix64 as the device */
+int dpr_msa_boot_weights(uint64_t seed, int64_t replicate, int64_t L, int32_t *out);
+/* host only, no GPU: main_* and rep_* are merge logs of dpr_nj_run (n-2 entries each, slots as there; the realID bookkeeping
+ * of writeNewickFromMerges names internal node n+k after iteration k).  counts[k] (k < n-2) is incremented when the
+ * replicate tree contains the split of the main tree's internal node n+k; entries of nodes whose split is trivial (a side
+ * with fewer than 2 tips) are left untouched.  Splits are compared as 128-bit XOR hashes of their side without tip 0. */
+int dpr_split_support(int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x, const int32_t *rep_y,
+                      int32_t *counts);
+/* in-place sum of `count` host integers over the context's ranks (RCCL or the shared region's device windows); nothing
+ * to do with one rank */
+int dpr_comm_sum_i32(dpr_ctx *ctx, int32_t *host_inout, int64_t count);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
