@@ -13,6 +13,7 @@ SRC_MSA, SRC_MASH, SRC_MATRIX = 1, 2, 3
 DIST_UNCORRECTED, DIST_JC = 1, 2
 
 c_i32p = C.POINTER(C.c_int32)
+c_i64p = C.POINTER(C.c_int64)
 c_u64p = C.POINTER(C.c_uint64)
 c_f64p = C.POINTER(C.c_double)
 
@@ -138,6 +139,10 @@ def load_library():
     L.dpr_msa_boot_weights.argtypes = [C.c_uint64, C.c_int64, C.c_int64, c_i32p]
     L.dpr_split_support.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]
     L.dpr_comm_sum_i32.argtypes = [C.c_void_p, c_i32p, C.c_int64]
+    L.dpr_transfer_support.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
+    L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
+    L.dpr_ctx_set_tbe_lds.argtypes = [C.c_void_p, C.c_int64]
+    L.dpr_comm_sum_i64.argtypes = [C.c_void_p, c_i64p, C.c_int64]
     _LIB = L
     return L
 
@@ -253,6 +258,23 @@ def split_support(n, main_x, main_y, rep_x, rep_y, counts=None):
     assert counts.dtype == np.int32 and counts.flags.c_contiguous and len(counts) >= n - 2
     _chk(lib, lib.dpr_split_support(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), _p(counts, c_i32p)))
     return counts
+
+
+def _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum):
+    logs = [np.ascontiguousarray(np.asarray(a, dtype=np.int32)[: n - 2]) for a in (main_x, main_y, rep_x, rep_y)]
+    if phi_sum is None:
+        phi_sum = np.zeros(max(n - 2, 1), dtype=np.int64)
+    assert phi_sum.dtype == np.int64 and phi_sum.flags.c_contiguous and len(phi_sum) >= n - 2
+    return logs, phi_sum
+
+
+def transfer_support_host(n, main_x, main_y, rep_x, rep_y, phi_sum=None):
+    """phi_sum[k] (internal node n+k of the main merge log, min(|A|, n-|A|) >= 2) + the transfer distance phi of its clade to
+    the replicate tree (host only)"""
+    lib = load_library()
+    (mx, my, rx, ry), phi_sum = _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum)
+    _chk(lib, lib.dpr_transfer_support_host(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), _p(phi_sum, c_i64p)))
+    return phi_sum
 
 
 def pack4_many(seqs):
@@ -649,6 +671,23 @@ class Dipper:
         """in-place integer sum over the context's ranks"""
         a = np.ascontiguousarray(values, dtype=np.int32)
         _chk(self.L, self.L.dpr_comm_sum_i32(self.h, _p(a, c_i32p), len(a)))
+        return a
+
+    def transfer_support(self, n, main_x, main_y, rep_x, rep_y, phi_sum=None):
+        """transfer_support_host's numbers, computed on the device"""
+        (mx, my, rx, ry), phi_sum = _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum)
+        _chk(self.L, self.L.dpr_transfer_support(self.h, n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p),
+                                                 _p(phi_sum, c_i64p)))
+        return phi_sum
+
+    def set_tbe_lds(self, nbytes):
+        """test hook: LDS budget of transfer_support's tables (0 = its own rule; below one node's table: global memory)"""
+        _chk(self.L, self.L.dpr_ctx_set_tbe_lds(self.h, nbytes))
+
+    def comm_sum_i64(self, values):
+        """in-place 64-bit integer sum over the context's ranks"""
+        a = np.ascontiguousarray(values, dtype=np.int64)
+        _chk(self.L, self.L.dpr_comm_sum_i64(self.h, _p(a, c_i64p), len(a)))
         return a
 
     def msa_counts(self, row):

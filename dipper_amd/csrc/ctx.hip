@@ -171,6 +171,7 @@ int dpr_destroy(dpr_ctx* c)
     mash_free(c->mash);
     place_free(c->place);
     exact_free(c->exact);
+    tbe_free(c->tbe);
     if (c->place_trace) (void)hipFree(c->place_trace);
     if (c->packed_lower) (void)hipFree(c->packed_lower);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);

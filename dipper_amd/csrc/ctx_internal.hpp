@@ -46,6 +46,8 @@ struct dpr_ctx {
     dpr::MashBuffers mash;
     dpr::PlaceBuffers place;
     dpr::ExactBuffers exact;
+    dpr::TbeBuffers tbe;
+    int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip
     double* packed_lower = nullptr;  // MATRIX source, device
     int64_t n_input = 0;

@@ -403,6 +403,23 @@ int msa_dist_rows(const MsaBuffers& m, NjBuffers& b, int dist_type, hipStream_t 
 int msa_dist_tile_edge(int dist_type);   // rows/columns per job tile of msa_dist_jobs
 int msa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s);
 
+// ---- transfer bootstrap expectation (tbe.hip) ----------------------------------------------------------------------------
+// The main tree is uploaded when its merge log differs from the last one (host copy kept): once per command.
+struct TbeBuffers {
+    int64_t n = 0, cap = 0;              // tips of the uploaded main tree; tips the buffers hold
+    std::vector<int32_t> hx, hy;         // the uploaded main merge log
+    std::vector<int32_t> mpos;           // main-order rank of every leaf
+    std::vector<int32_t> node;           // k of every listed main node (internal node n+k with min(|A|, n-|A|) >= 2)
+    std::vector<int32_t> hphi;           // phi of the listed nodes, copied back
+    int2* main_iv = nullptr;             // [listed] main clade as [S, E) in the main tree's DFS leaf order
+    int32_t* m = nullptr;                // [n] main-order rank of the leaf at every replicate DFS position
+    int2* rep_iv = nullptr;              // [n-2] replicate internal node n+k as [s, e) in the replicate's DFS leaf order
+    int32_t* phi = nullptr;              // [listed]
+    uint4* scratch = nullptr;            // tables of the global-memory variant (none until a tree needs it)
+    size_t scratch_bytes = 0;
+};
+void tbe_free(TbeBuffers& t);
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of 512 tips the (value -> tips, positions) postings
 struct MashIndex {

@@ -255,11 +255,16 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
 struct BootstrapOptions {
     int64_t replicates = 0;      // --bootstrap N (0 = off)
     uint64_t seed = 1;           // --bootstrap-seed S
+    bool tbe = false;            // --bootstrap-metric tbe: transfer bootstrap expectation instead of Felsenstein's
 };
 // Support labels of the main tree (merge log mx / my of n tips) from summed counts over `replicates` replicates: the integer
 // percentage, rounded half up, for internal nodes with a non-trivial split, -1 elsewhere.
 std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
                                    const std::vector<int32_t>& counts, int64_t replicates);
+// TBE labels from the per-node sums of phi (dpr_transfer_support) over `replicates` replicates: den = replicates (p - 1),
+// (200 (den - sum) + den) / (2 den) for internal nodes with p = min(|A|, n - |A|) >= 2, -1 elsewhere.
+std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
+                                    const std::vector<int64_t>& phi_sum, int64_t replicates);
 // The NJ tree of -i m -o t with --bootstrap: the main tree exactly as findNeighbourJoiningTree builds it, then this rank's
 // replicates (r mod world == rank) on `dev` (one rank) or on a rank-local second context over `packed4` (several ranks), one
 // integer sum of the split counts over the ranks, and the labelled Newick.

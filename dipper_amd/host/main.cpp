@@ -73,7 +73,10 @@ static const char* kHelp =
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
     "                              -i m -o t with conventional NJ only (-m 2, or -m 0 below 30000)\n"
-    "  --bootstrap-seed arg        Seed of the replicates' column draws (unsigned 64-bit, default 1)\n";
+    "  --bootstrap-seed arg        Seed of the replicates' column draws (unsigned 64-bit, default 1)\n"
+    "  --bootstrap-metric arg      fbp (default): Felsenstein support, the share of replicates that hold\n"
+    "                              a split exactly; tbe: transfer bootstrap expectation, one minus the\n"
+    "                              mean share of a split's taxa that must move to reach a replicate\n";
 
 struct Opt { const char* lng; char sht; bool has_arg; };
 static const Opt kOpts[] = {
@@ -83,7 +86,7 @@ static const Opt kOpts[] = {
     { "add", 'a', false }, { "input-tree", 't', true }, { "help", 'h', false },
     { "seed", 0, true }, { "device", 0, true }, { "gpus", 0, true }, { "devices", 0, true }, { "transport", 0, true },
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true },
-    { "bootstrap", 0, true }, { "bootstrap-seed", 0, true },
+    { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -231,6 +234,7 @@ int main(int argc, char** argv)
     // --bootstrap: what the arguments alone decide is checked here, before any input is read or a GPU touched
     BootstrapOptions boot;
     if (vm.count("bootstrap-seed") && !vm.count("bootstrap")) usageError("--bootstrap-seed needs --bootstrap");
+    if (vm.count("bootstrap-metric") && !vm.count("bootstrap")) usageError("--bootstrap-metric needs --bootstrap");
     if (vm.count("bootstrap")) {
         auto whole = [](const std::string& v, bool sign_ok) {
             if (v.empty() || v.size() > 20) return false;
@@ -249,6 +253,11 @@ int main(int argc, char** argv)
                 if (!whole(sv, false)) throw 0;
                 boot.seed = (uint64_t)std::stoull(sv);
             } catch (...) { usageError("--bootstrap-seed: an unsigned 64-bit integer"); }
+        }
+        if (vm.count("bootstrap-metric")) {
+            const std::string mv = vm["bootstrap-metric"];
+            if (mv != "fbp" && mv != "tbe") usageError("--bootstrap-metric: fbp or tbe");
+            boot.tbe = mv == "tbe";
         }
         const std::string in = strOr(vm, "input-format", "r"), out = strOr(vm, "output-format", "t"), al = strOr(vm, "algorithm", "0");
         if (in != "m") usageError("--bootstrap needs aligned sequences (-i m)");

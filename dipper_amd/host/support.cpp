@@ -5,6 +5,8 @@
 // (host) into per-node counts.  One rank: the replicates reuse the main context and its NJ buffers.  Several ranks: each runs
 // them on a rank-local second context on its own device (one rank, so no plan of the joined context -- and no collective --
 // reaches the replicate loop).  One integer sum over the ranks combines the counts; rank 0 writes the labelled Newick.
+// --bootstrap-metric tbe: dpr_transfer_support (device) in place of dpr_split_support, per-node sums of phi in place of the
+// counts (one 64-bit sum over the ranks), transferLabels in place of supportLabels.
 #include "dipper_host.hpp"
 
 #include <chrono>
@@ -12,12 +14,9 @@
 
 namespace dipper {
 
-std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
-                                   const std::vector<int32_t>& counts, int64_t replicates)
+// clade sizes with the realID bookkeeping of writeNewickFromMerges
+static std::vector<int64_t> cladeSizes(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my)
 {
-    std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
-    if (n <= 3 || replicates <= 0) return labels;
-    // clade sizes with the realID bookkeeping of writeNewickFromMerges
     std::vector<int64_t> size((size_t)(2 * n - 2), 1);
     std::vector<int32_t> real((size_t)n);
     for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
@@ -27,9 +26,33 @@ std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, co
         real[(size_t)x] = (int32_t)(n + it);
         real[(size_t)y] = real[(size_t)(n - it - 1)];
     }
+    return size;
+}
+
+std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
+                                   const std::vector<int32_t>& counts, int64_t replicates)
+{
+    std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
+    if (n <= 3 || replicates <= 0) return labels;
+    const std::vector<int64_t> size = cladeSizes(n, mx, my);
     for (int64_t k = 0; k < n - 2; ++k) {
         const int64_t s = size[(size_t)(n + k)];
         if (s >= 2 && s <= n - 2) labels[(size_t)k] = (int32_t)((200 * (int64_t)counts[(size_t)k] + replicates) / (2 * replicates));
+    }
+    return labels;
+}
+
+std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
+                                    const std::vector<int64_t>& phi_sum, int64_t replicates)
+{
+    std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
+    if (n <= 3 || replicates <= 0) return labels;
+    const std::vector<int64_t> size = cladeSizes(n, mx, my);
+    for (int64_t k = 0; k < n - 2; ++k) {
+        const int64_t p = std::min(size[(size_t)(n + k)], n - size[(size_t)(n + k)]);
+        if (p < 2) continue;
+        const int64_t den = replicates * (p - 1), num = den - phi_sum[(size_t)k];
+        labels[(size_t)k] = (int32_t)((200 * num + den) / (2 * den));
     }
     return labels;
 }
@@ -55,6 +78,7 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
 
     const auto tb0 = Clock::now();
     std::vector<int32_t> counts((size_t)k, 0);
+    std::vector<int64_t> phi_sum(bo.tbe ? (size_t)k : 0, 0);
     dpr_ctx* rctx = dev.ctx;
     auto fail = [&](int64_t r, const char* what, int rc) {
         die("ERROR: bootstrap replicate " + std::to_string(r) + ": " + what + " failed (" + std::to_string(rc) + "): " + dpr_last_error());
@@ -80,7 +104,12 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
         const int64_t rdone = dpr_nj_run(rctx, -1, rx.data(), ry.data(), rbx.data(), rby.data(), &rlast);
         if (rdone < 0) fail(r, "dpr_nj_run", (int)rdone);
         const auto t3 = Clock::now();
-        if (int rc = dpr_split_support(n, mx.data(), my.data(), rx.data(), ry.data(), counts.data())) fail(r, "dpr_split_support", rc);
+        if (bo.tbe) {
+            if (int rc = dpr_transfer_support(rctx, n, mx.data(), my.data(), rx.data(), ry.data(), phi_sum.data()))
+                fail(r, "dpr_transfer_support", rc);
+        } else if (int rc = dpr_split_support(n, mx.data(), my.data(), rx.data(), ry.data(), counts.data())) {
+            fail(r, "dpr_split_support", rc);
+        }
         const auto t4 = Clock::now();
         ++mine;
         mine_ms += ms(t0, t4);
@@ -88,18 +117,22 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
             double dist_ms = 0, nj_ms = 0;
             dpr_get_timing(rctx, &dist_ms, &nj_ms);
             std::cerr << "  replicate " << r << ": resample " << ms(t0, t1) << " ms, distances " << ms(t1, t2) << " ms (device "
-                      << dist_ms << "), NJ " << ms(t2, t3) << " ms (device " << nj_ms << "), split count " << ms(t3, t4) << " ms\n";
+                      << dist_ms << "), NJ " << ms(t2, t3) << " ms (device " << nj_ms << "), "
+                      << (bo.tbe ? "transfer support " : "split count ") << ms(t3, t4) << " ms\n";
         }
     }
     if (rctx != dev.ctx) dpr_destroy(rctx);
     else gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, -1), "dpr_msa_resample");
-    if (n > 2) gpuCheck(dpr_comm_sum_i32(dev.ctx, counts.data(), n - 2), "dpr_comm_sum_i32");
+    if (n > 2 && bo.tbe) gpuCheck(dpr_comm_sum_i64(dev.ctx, phi_sum.data(), n - 2), "dpr_comm_sum_i64");
+    else if (n > 2) gpuCheck(dpr_comm_sum_i32(dev.ctx, counts.data(), n - 2), "dpr_comm_sum_i32");
     const auto tb1 = Clock::now();
 
-    const std::vector<int32_t> labels = supportLabels(n, mx, my, counts, bo.replicates);
+    const std::vector<int32_t> labels = bo.tbe ? transferLabels(n, mx, my, phi_sum, bo.replicates)
+                                               : supportLabels(n, mx, my, counts, bo.replicates);
     writeNewickFromMerges(output_, name, mx, my, bx, by, last, &labels);
     std::cerr << "Bootstrap: " << bo.replicates << " replicates (seed " << bo.seed << ") in " << (long long)ms(tb0, tb1) << " ms, "
-              << (mine ? mine_ms / (double)mine : 0.0) << " ms per replicate, " << ri.world << " ranks\n";
+              << (mine ? mine_ms / (double)mine : 0.0) << " ms per replicate, " << ri.world << " ranks"
+              << (bo.tbe ? ", metric tbe (transfer bootstrap expectation)" : "") << "\n";
 }
 
 }  // namespace dipper

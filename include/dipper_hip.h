@@ -402,6 +402,27 @@ int dpr_split_support(int64_t n, const int32_t *main_x, const int32_t *main_y, c
  * to do with one rank */
 int dpr_comm_sum_i32(dpr_ctx *ctx, int32_t *host_inout, int64_t count);
 
+/* ---- transfer bootstrap expectation (TBE, Lemoine et al. 2018; no reference counterpart) ---------------------------------
+ * Main internal node n+k (merge-log numbering as dpr_split_support) has clade A, p = min(|A|, n - |A|); only nodes with p >= 2
+ * are computed.  A replicate tree T* has the clades L_v of all its nodes, leaves included:
+ *   h = |A| + |L_v| - 2 |A & L_v|,  delta(A, v) = min(h, n - h),  phi(A, T*) = min_v delta(A, v), in [0, p - 1].
+ * Over R replicates with S = sum of phi, den = R (p - 1): the TBE label is (200 (den - S) + den) / (2 den). */
+/* On the device (tbe.hip): phi_sum[k] += phi(A_k, replicate) for the nodes with p >= 2; the other entries are left untouched.
+ * main_* and rep_* are merge logs of dpr_nj_run (n-2 entries each); a bad log is DPR_ERR_ARG.  The main tree is uploaded when
+ * its log differs from the previous call's (once per command); the replicate's DFS intervals are built on the host, O(n). */
+int dpr_transfer_support(dpr_ctx *ctx, int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x,
+                         const int32_t *rep_y, int64_t *phi_sum);
+/* host only, no GPU: the same numbers by a plain restatement (per main node, |A & L_v| bottom-up over the replicate's merge
+ * order; host threads) -- the test reference */
+int dpr_transfer_support_host(int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x, const int32_t *rep_y,
+                              int64_t *phi_sum);
+/* test hook: LDS bytes dpr_transfer_support may give one workgroup's tables (16 (n/64 + 1) bytes per main node, up to 8 nodes
+ * per workgroup; 0 = its own rule: 64 KiB, or one node up to 159 KiB).  A budget below one node's table puts the tables in
+ * global memory. */
+int dpr_ctx_set_tbe_lds(dpr_ctx *ctx, int64_t bytes);
+/* in-place sum of `count` host 64-bit integers over the context's ranks; nothing to do with one rank */
+int dpr_comm_sum_i64(dpr_ctx *ctx, int64_t *host_inout, int64_t count);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
