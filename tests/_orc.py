@@ -98,6 +98,28 @@ class Oracle:
         self.lib.orc_msa_dist_lower(_p(p, c_u64p), n, L, dist_type, _p(D, c_f64p), ld)
         return D
 
+    def msa_dist_row(self, packed4, L, dist_type, row, ncols):
+        """distances of sequence `row` against sequences 0 .. ncols - 1"""
+        out = np.zeros(ncols, dtype=np.float64)
+        p = np.ascontiguousarray(packed4)
+        self.lib.orc_msa_dist_row(_p(p, c_u64p), L, dist_type, row, ncols, _p(out, c_f64p))
+        return out
+
+    def msa_dist_lower_mt(self, packed4, L, dist_type, threads=16):
+        """msa_dist_lower, row blocks on a pool of at most `threads` threads (ctypes releases the GIL during the call; every
+        row is the oracle's own loop, so the result does not depend on the thread count)"""
+        from concurrent.futures import ThreadPoolExecutor
+        p = np.ascontiguousarray(packed4)
+        n = p.shape[0]
+        D = np.zeros((n, n), dtype=np.float64)
+
+        def rows(r0):
+            for r in range(max(r0, 1), min(r0 + 8, n)):
+                self.lib.orc_msa_dist_row(_p(p, c_u64p), L, dist_type, r, r, _p(D[r], c_f64p))
+        with ThreadPoolExecutor(max(1, min(threads, 16, _os.cpu_count() or 1))) as ex:
+            list(ex.map(rows, range(0, n, 8)))
+        return D
+
     # ---- NJ ---------------------------------------------------------------------------------
     def row_sums(self, D):
         n, ld = D.shape

@@ -467,3 +467,191 @@ def reads_reorder(reads, order):
     tot = int(new_nw.sum())
     idx = np.repeat(starts - np.concatenate(([0], np.cumsum(new_nw)[:-1])), new_nw) + np.arange(tot)
     return np.ascontiguousarray(flat[idx]), new_off, np.ascontiguousarray(ln[order])
+
+
+# ---- aligned-sequence distances: one comparison rule against the oracle, and hostile alignments -------------------------------
+
+MSA_ULP_BOUND = 4      # types 2-5: one libm log against one ocml log per log term (each within 1 ulp), terms of one sign
+MSA_ULP_SEEN = {}      # dist_type -> the largest ulp distance assert_msa_dist has met in this process
+
+
+def _ulp_key(a):
+    """binary64 -> uint64 that orders like the values (-0.0 and +0.0 meet at one key)"""
+    i = np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+    return (np.where(i < 0, np.int64(-2**63) - i, i).astype(np.int64).view(np.uint64) + np.uint64(2**63))
+
+
+def ulp_distance(a, b):
+    ka, kb = _ulp_key(a), _ulp_key(b)
+    return np.where(ka > kb, ka - kb, kb - ka)
+
+
+def assert_msa_dist(got, ref, dist_type, what=""):
+    """The rule every aligned-sequence distance assertion uses, kernel against oracle, cell by cell:
+      types 1 and 6   bit-identical, signed zeros included (no libm call; both sides built with -ffp-contract=off);
+      types 2-5       at most MSA_ULP_BOUND ulp apart;
+      non-finite      the same class (NaN / +inf / -inf); NaN payloads are not compared.
+    Returns the largest ulp distance among the finite cells."""
+    got = np.asarray(got, dtype=np.float64).ravel()
+    ref = np.asarray(ref, dtype=np.float64).ravel()
+    assert got.shape == ref.shape, what
+    ng, nr = np.isnan(got), np.isnan(ref)
+    bad = np.flatnonzero(ng != nr)
+    assert bad.size == 0, f"{what} type {dist_type}: NaN in one only at {bad[:8]}: got {got[bad[:8]]} want {ref[bad[:8]]}"
+    fin = np.isfinite(ref)
+    inf = ~fin & ~nr
+    bad = np.flatnonzero(inf & (got != ref))
+    assert bad.size == 0, f"{what} type {dist_type}: infinities differ at {bad[:8]}: got {got[bad[:8]]} want {ref[bad[:8]]}"
+    bad = np.flatnonzero(fin & ~np.isfinite(got))
+    assert bad.size == 0, f"{what} type {dist_type}: non-finite where the oracle is finite at {bad[:8]}: {got[bad[:8]]}"
+    if dist_type in (1, 6):
+        g, r = got[~nr].view(np.uint64), ref[~nr].view(np.uint64)
+        bad = np.flatnonzero(g != r)
+        assert bad.size == 0, f"{what} type {dist_type}: not bit-identical at {bad[:8]}: got {got[~nr][bad[:8]]!r} want {ref[~nr][bad[:8]]!r}"
+        worst = 0
+    else:
+        u = ulp_distance(got[fin], ref[fin])
+        worst = int(u.max()) if u.size else 0
+        bad = np.flatnonzero(u > MSA_ULP_BOUND)
+        assert bad.size == 0, (f"{what} type {dist_type}: {bad.size} cells more than {MSA_ULP_BOUND} ulp from the oracle, max {worst}: "
+                               f"got {got[fin][bad[:4]]!r} want {ref[fin][bad[:4]]!r}")
+    MSA_ULP_SEEN[dist_type] = max(MSA_ULP_SEEN.get(dist_type, 0), worst)
+    return worst
+
+
+_SITE = 512            # sites per 16-word stage of the pair kernel's staging (16 words of 32 sites)
+
+
+def _base_alignment(rng, n, L, mean_bl=3e-3):
+    return [bytearray(s) for s in synth_alignment(rng, n, L, mean_bl=mean_bl, lo=1e-4, hi=3e-2)]
+
+
+def _put(seqs, s, site, ch):
+    """one not-a-base code at `site` of sequence s; every other sequence gets an A there, so that a path that lets the
+    not-a-base code pass as a base (its planes read A) miscounts against every one of them"""
+    for t in range(len(seqs)):
+        if seqs[t][site] in b"ACGT":
+            seqs[t][site] = ord("A")
+    seqs[s][site] = ord(ch)
+
+
+def msa_single_gaps(L, n=130, seed=0):
+    """~26 sequences carry one '-' or 'N' each, every other sequence is clean: sequence index mod 64 in {0, 15, 16, 47, 48, 63}
+    (the first and last row of each wavefront) and some more, in every 64-row tile (the last one partial at n = 130), at bit 0
+    of a stage's first word, bit 31 of its last word, inside a middle quad, at site 0 and at site L - 1; two pairs of sequences in
+    different tiles share their site (the word holds a not-a-base position on both sides of an off-diagonal tile)."""
+    rng = np.random.default_rng(1000 + L + seed)
+    seqs = _base_alignment(rng, n, L)
+    nst = (L + _SITE - 1) // _SITE
+    who = [s for s in (0, 15, 16, 47, 48, 63, 64, 79, 80, 111, 112, 127, 128, 129, 1, 31, 33, 62, 65, 94, 97, 126, 113, 50)
+           if s < n]
+    spots = lambda st: [st * _SITE, st * _SITE + 15 * 32 + 31, st * _SITE + 5 * 32 + 17, st * _SITE + 10 * 32 + 3,
+                        st * _SITE + 31, st * _SITE + 15 * 32]
+    placed = []
+    for i, s in enumerate(who):
+        if i == 0:
+            site = 0
+        elif i == 1:
+            site = L - 1
+        else:
+            st = (i * 7) % nst
+            site = min(spots(st)[i % 6], L - 1)
+        _put(seqs, s, site, "-N"[i & 1])
+        placed.append((s, site))
+    for a, b in ((0, 129), (16, 80)):         # shared sites: both sides of tiles (2, 0) and (1, 0)
+        if b < n:
+            site = min(nst - 1, 2) * _SITE + 7 * 32 + 9
+            _put(seqs, a, site, "-")
+            seqs[b][site] = ord("N")
+    return [bytes(s) for s in seqs]
+
+
+def msa_stage63_gaps(L, n=70, seed=0):
+    """single gaps only in stages 62, 63, 64, 70 and the last (where they exist; stages from 63 on share bit 63 of the
+    per-sequence stage bitmap), each in its own sequence, in both 64-row tiles"""
+    rng = np.random.default_rng(2000 + L + seed)
+    seqs = _base_alignment(rng, n, L, mean_bl=2e-3)
+    nst = (L + _SITE - 1) // _SITE
+    stages = [st for st in (62, 63, 64, 70, nst - 1) if st < nst]
+    tile0, tile1 = [5, 20, 40, 33, 50], [66, 68, 65, 67, 69]
+    for i, st in enumerate(stages):
+        for j, s in enumerate((tile0[i], tile1[i])):
+            if s < n:
+                _put(seqs, s, min(st * _SITE + [0, 15 * 32 + 31, 6 * 32 + 13][(i + j) % 3], L - 1), "-N"[j])
+    return [bytes(s) for s in seqs]
+
+
+def msa_band_edges(L, seed=0):
+    """pairs (2i, 2i + 1) that share exactly g invalid sites, g in {0, 1, 14, 15, 16, 17} (the band table covers g <= 15),
+    and sequences with 1 .. 20 gaps on one side only"""
+    rng = np.random.default_rng(3000 + L + seed)
+    gs = [0, 1, 14, 15, 16, 17]
+    one = [1, 5, 15, 16, 20]
+    n = 2 * len(gs) + len(one) + 3
+    seqs = _base_alignment(rng, n, L, mean_bl=3e-3)
+    sites = rng.permutation(L)
+    k = 0
+    for i, g in enumerate(gs):
+        for site in sites[k:k + g]:
+            seqs[2 * i][site] = ord("-")
+            seqs[2 * i + 1][site] = ord("N")
+        k += g
+    for j, g in enumerate(one):
+        for site in sites[k:k + g]:
+            seqs[2 * len(gs) + j][site] = ord("-N"[site & 1])
+        k += g
+    return [bytes(s) for s in seqs]
+
+
+def msa_density(L, n, rate, runs=False, seed=0):
+    """scattered (or indel-like runs of) '-' / 'N' at `rate`, plus an all-gap and an all-N sequence, duplicated sequences and
+    unrelated (saturated) ones"""
+    rng = np.random.default_rng(4000 + L + n + int(rate * 1000) + 7 * runs + seed)
+    seqs = _base_alignment(rng, n, L, mean_bl=4e-3)
+    for s in seqs:
+        if runs:
+            k = 0
+            while k < L:
+                k += int(rng.geometric(rate / 4.0))
+                ln = int(rng.geometric(0.25))
+                s[k:min(k + ln, L)] = b"-" * (min(k + ln, L) - max(min(k, L), 0))
+                k += ln
+        else:
+            hit = np.flatnonzero(rng.random(L) < rate)
+            for site in hit:
+                s[site] = ord("-N"[site & 1])
+    if n >= 4:
+        seqs[n // 3] = bytearray(b"-" * L)
+        seqs[n - 1] = bytearray(b"N" * L)
+    if n >= 6:
+        seqs[1] = bytearray(seqs[n // 2])                                  # a duplicate
+        seqs[n - 2] = bytearray(BASES[rng.integers(0, 4, size=L)].tobytes())   # unrelated to everything
+    return [bytes(s[:L]) for s in seqs]
+
+
+def msa_composition(L, n, gc, seed=0):
+    """base composition skewed to GC (gc = 0.7) or AT (gc = 0.3), transitions ~10 times as frequent as transversions, and the
+    degenerate pairs of the oracle's hand-built cases: identical, A<->C only, A<->T only (Tamura's c = 0), all transitions (1 - 2p
+    - q < 0), an all-gap sequence and one with a single valid site"""
+    rng = np.random.default_rng(5000 + L + n + int(gc * 100) + seed)
+    probs = np.array([1 - gc, gc, gc, 1 - gc]) / 2.0
+    root = rng.choice(4, size=L, p=probs).astype(np.uint8)
+    out = []
+    for i in range(n):
+        s = root.copy()
+        rate = 0.002 + 0.3 * (i / max(n - 1, 1))
+        hit = np.flatnonzero(rng.random(L) < rate)
+        tv = rng.random(hit.size) < 1.0 / 11.0
+        s[hit[~tv]] ^= 2                                                    # A<->G, C<->T
+        s[hit[tv]] ^= rng.choice(np.array([1, 3], dtype=np.uint8), size=int(tv.sum()))
+        out.append(bytearray(BASES[s].tobytes()))
+    if n >= 8:
+        r0 = bytes(out[0])
+        out[1] = bytearray(r0)
+        out[2] = bytearray(r0.replace(b"A", b"C"))
+        out[3] = bytearray(r0.replace(b"A", b"T"))
+        out[4] = bytearray(BASES[(np.frombuffer(r0, np.uint8) == BASES[:, None]).argmax(0) ^ 2].tobytes())
+        out[5] = bytearray(b"-" * L)
+        out[6] = bytearray(b"N" * L)
+        out[6][L // 2] = ord("G")
+    return [bytes(s) for s in out]

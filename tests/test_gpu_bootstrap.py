@@ -23,19 +23,22 @@ def replicate_seqs(seqs, seed, r):
     return [np.frombuffer(s, dtype=np.uint8)[idx].tobytes() for s in seqs]
 
 
-@pytest.mark.parametrize("L", [33, 700, 2500])
+@pytest.mark.parametrize("L", [33, 700, 2080, 2500, 33000])
 @pytest.mark.parametrize("invalid", [0.0, 0.02])
-def test_resample_equals_host_replicate(L, invalid):
+def test_resample_equals_host_replicate(orc, L, invalid):
+    """the resampled planes (and, through msa_restage, their stage bitmap) equal an upload of the host-built replicate, and the
+    replicate's distances equal the oracle's on that replicate under _util.assert_msa_dist, every type"""
     import dipper_amd
     from dipper_amd import capi
     rng = np.random.default_rng(L + int(invalid * 1000))
-    n = 257
+    n = 257 if L < 10000 else 40
     seqs = _util.synth_alignment(rng, n=n, L=L, mean_bl=2e-3, lo=2e-4, hi=2e-2, invalid_frac=invalid)
     seed, r = 11, 3
     a, b = dipper_amd.Dipper(0), dipper_amd.Dipper(0)
     try:
         a.set_msa(capi.pack4_many(seqs), L)
-        b.set_msa(capi.pack4_many(replicate_seqs(seqs, seed, r)), L)
+        rep_packed = capi.pack4_many(replicate_seqs(seqs, seed, r))
+        b.set_msa(rep_packed, L)
         orig = {}
         for d in range(1, 7):
             a.dist_matrix(capi.SRC_MSA, d)
@@ -47,10 +50,12 @@ def test_resample_equals_host_replicate(L, invalid):
             b.dist_matrix(capi.SRC_MSA, d)
             Da, Db = a.matrix(), b.matrix()
             assert np.array_equal(np.isnan(Da), np.isnan(Db)) and np.array_equal(Da, Db, equal_nan=True), d
-            blk_a, _ = a.msa_dist_block(40, 100, n, dist_type=d)
-            blk_b, _ = b.msa_dist_block(40, 100, n, dist_type=d)
+            blk_a, _ = a.msa_dist_block(min(40, n - 1), min(100, n - min(40, n - 1)), n, dist_type=d)
+            blk_b, _ = b.msa_dist_block(min(40, n - 1), min(100, n - min(40, n - 1)), n, dist_type=d)
             assert np.array_equal(blk_a, blk_b, equal_nan=True), d
-        for row in (1, 100, n - 1):
+            lo = np.tril_indices(n, -1)
+            _util.assert_msa_dist(Da[lo], orc.msa_dist_lower_mt(rep_packed, L, d)[lo], d, f"replicate L={L}")
+        for row in (1, min(100, n - 1), n - 1):
             ua, ma = a.msa_counts(row)
             ub, mb = b.msa_counts(row)
             assert np.array_equal(ua, ub) and np.array_equal(ma, mb)

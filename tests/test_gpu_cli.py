@@ -94,6 +94,42 @@ def test_msa_jc_default_shuffle(tmp_path, orc):
     assert np.allclose(P1, P2, rtol=2e-5, atol=1e-9)
 
 
+@pytest.mark.parametrize("dt", [3, 4, 5, 6])
+def test_msa_other_models_end_to_end(tmp_path, orc, dt):
+    """-i m -m 2 -d 3..6 (Tajima-Nei, K2P, Tamura, Jin-Nei) on a GC-rich, transition-biased alignment with finite distances: -d 6 uses no libm call, so
+    the Newick text equals the one built from the oracle's NJ on the oracle's distances; for 3-5 the splits are equal and the
+    patristic distances within 2e-5 relative"""
+    rng = np.random.default_rng(23 + dt)
+    n, L = 100, 2500
+    probs = np.array([0.15, 0.35, 0.35, 0.15])
+    root = rng.choice(4, size=L, p=probs).astype(np.uint8)
+    seqs = []
+    for i in range(n):
+        t = root.copy()
+        hit = np.flatnonzero(rng.random(L) < 0.01 + 0.1 * rng.random())
+        tv = rng.random(hit.size) < 0.3       # transversions A<->T, C<->G: Tamura's c stays large enough for finite distances
+        t[hit[~tv]] ^= 2
+        t[hit[tv]] ^= 3
+        seqs.append(_util.BASES[t].tobytes())
+    names = [f"S{i}" for i in range(n)]
+    fa = tmp_path / "c.fa"
+    _util.write_fasta(str(fa), names, seqs)
+    out = tmp_path / "o.nwk"
+    r = run("-i", "m", "-I", str(fa), "-O", str(out), "-m", "2", "-d", str(dt), "--seed", "-1")
+    assert r.returncode == 0, r.stderr
+    D = orc.msa_dist_lower(orc.pack4_many(seqs), L, dt)
+    assert np.all(np.isfinite(D))
+    ref = orc.nj_run(D)
+    expect = _util.newick_from_merges(names, ref["merge_x"], ref["merge_y"], ref["bl_x"], ref["bl_y"], ref["last_d"])
+    got = out.read_text()
+    if dt == 6:
+        assert got == expect
+    else:
+        assert _util.splits(got, names) == _util.splits(expect, names)
+        P1, P2 = _util.patristic(got, names), _util.patristic(expect, names)
+        assert np.allclose(P1, P2, rtol=2e-5, atol=1e-9)
+
+
 def _api_matrix(kind, seqs, L=None, dt=2):
     import dipper_amd
     from dipper_amd import capi

@@ -63,7 +63,7 @@ def test_dc_msa(gpu, orc, n, B, flags):
     assert sorted(_util.parse_newick(nw)[2].values()) == sorted(names)   # every tip exactly once
 
 
-@pytest.mark.parametrize("dist_type", [1, 4, 5])
+@pytest.mark.parametrize("dist_type", [1, 2, 3, 4, 5, 6])
 def test_dc_msa_big_cluster_and_other_models(gpu, orc, dist_type):
     """one cluster of ~150 members: several 64x64 (32x32) pair tiles per cluster, long BFS frontiers"""
     from dipper_amd import capi

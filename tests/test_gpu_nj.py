@@ -140,15 +140,7 @@ def test_msa_dist_and_nj(gpu, orc, n, L, inv):
         assert np.array_equal(M, M.T, equal_nan=True) and np.all(np.diag(M) == 0)
         D_ref = orc.msa_dist_lower(packed, L, dt)
         lo = np.tril_indices(n, -1)
-        a, b = M[lo], D_ref[lo]
-        if dt == capi.DIST_UNCORRECTED:
-            assert np.array_equal(a, b, equal_nan=True)          # pure integer/fp64 division
-        else:
-            ok = np.isfinite(b)
-            assert np.array_equal(np.isnan(a), np.isnan(b))
-            assert np.array_equal(np.isinf(a), np.isinf(b))
-            # tolerance of north_star: 1e-6 relative (libm log/sqrt differ in the last bits)
-            assert np.allclose(a[ok], b[ok], rtol=1e-11, atol=1e-300)
+        _util.assert_msa_dist(M[lo], D_ref[lo], dt, f"n={n} L={L}")      # types 1, 6 bit for bit; 2-5 within 4 ulp
         if np.all(np.isfinite(M)):
             ref = orc.nj_run(np.tril(M, -1))
             res = gpu.nj_run()
@@ -163,7 +155,7 @@ def test_msa_fast_stages_band_table_and_block_hook_equal_the_plain_kernel(gpu, o
     and distances of pairs with useful >= L - 15 come from a band table (msa.hip).  An alignment of 2 300 sites in
     which gaps sit in SOME stages of SOME sequences (runs inside one stage, a run across a stage boundary, a tip that is all
     gaps, 40 tips with an unknown base each in different stages, everything else clean): every type-1 / type-2 distance must equal
-    the kernel with both switched off (DPR_MSA_NO_FAST / DPR_MSA_NO_BAND) bit for bit, the oracle's at rtol 1e-11, and the block
+    the kernel with both switched off (DPR_MSA_NO_FAST / DPR_MSA_NO_BAND) bit for bit, the oracle's under _util.assert_msa_dist, and the block
     hook (the launcher of placement batches, --add and the divide-and-conquer assignment) must return the same numbers in both
     orientations."""
     import os
@@ -205,10 +197,7 @@ def test_msa_fast_stages_band_table_and_block_hook_equal_the_plain_kernel(gpu, o
         assert np.array_equal(got["fast", dt], got["plain", dt], equal_nan=True)
         ref = orc.msa_dist_lower(packed, L, dt)
         lo = np.tril_indices(n, -1)
-        a, b = got["fast", dt][lo], ref[lo]
-        assert np.array_equal(np.isnan(a), np.isnan(b))
-        ok = np.isfinite(b)
-        assert np.allclose(a[ok], b[ok], rtol=1e-11, atol=1e-300)
+        _util.assert_msa_dist(got["fast", dt][lo], ref[lo], dt, "fast stages")
     u_ref, m_ref = orc.msa_counts(packed, L)
     assert (u_ref[np.tril_indices(n, -1)] == L).mean() > 0.7          # most pairs are clean: the band table's first row
 

@@ -255,3 +255,74 @@ def test_rapidnj_style_baseline_is_exact_nj(orc, n):
     ref = orc.nj_run(np.tril(D, -1))
     nw2 = _util.newick_from_merges(names, ref["merge_x"], ref["merge_y"], ref["bl_x"], ref["bl_y"], ref["last_d"], fmt=repr)
     assert _util.splits(nw, names) == _util.splits(nw2, names)
+
+
+def _degenerate_alignment():
+    """Hand-built pairs for every count class of the six distance types (16 sites: the count fractions are binary64 numbers, so
+    an exactly singular cell is singular in fp64 too), plus skewed random rows of 37 sites whose fractions are not."""
+    s0 = b"ACGTACGTACGTACGT"
+    rows = [
+        s0,
+        s0,                                  # identical: p = q = 0, Tajima-Nei h = 0, Tamura c = 0
+        b"CCGTCCGTCCGTACGT",                 # A<->C only: no Tajima-Nei pair class counts it
+        b"TCGTTCGTACGTTCGT",                 # A<->T only: no C/G at a mismatch, Tamura c = 0
+        b"GTACGTACGTACGTAC",                 # transitions everywhere: 1 - 2p - q < 0
+        b"GTACGTACACGTACGT",                 # 2p + q = 1 exactly: log 0, 1 / 0
+        b"ACGTACGTAAAAAAAA",                 # 2q = 1 against s0's tail
+        b"GCGCGGCCGCGAGCGC",                 # GC-rich
+        b"GCACGGCTGCGAGTGC",                 # ... and its transitions
+        b"ATATTAATATTAAATA",                 # AT-rich
+        b"GTGTTAGTATTGAACA",                 # ... transition-biased
+        b"----------------",
+        b"NNNNNNNNNNNNNNNN",                 # all-N: useful = 0 against the all-gap row
+        b"-------A--------",                 # one valid site
+        b"nnnnnnnnnnnnnnnG",
+        b"AC-TAC-TNNNNACGT",
+        b"acgtACGTACGTACGT",                 # lower case is not a base
+    ]
+    rng = np.random.default_rng(5)
+    skew = []
+    for probs in ((0.15, 0.35, 0.35, 0.15), (0.35, 0.15, 0.15, 0.35)):
+        root = rng.choice(4, size=37, p=probs)
+        for _ in range(4):
+            s = root.copy()
+            hit = rng.random(37) < 0.3
+            s[hit] ^= 2                      # transitions (A<->G, C<->T) ...
+            tv = rng.random(37) < 0.05
+            s[tv] = (s[tv] + 1) & 3          # ... and a few transversions
+            t = bytearray(b"ACGT"[i] for i in s)
+            for k in rng.choice(37, size=3, replace=False):
+                t[k] = ord("-")
+            skew.append(bytes(t))
+    return rows, skew
+
+
+@pytest.mark.parametrize("dist_type", [1, 2, 3, 4, 5, 6])
+def test_msa_oracle_against_exact_reference(orc, dist_type, capsys):
+    """All six distance types of the oracle against the exact-rational / 50-digit reference (tests/_msa_ref.py), written from
+    the original program's formulas: regular cells at a relative 1e-12, special cells (0/0, x/0, log of 0 or of a negative
+    number) the same IEEE class, near-singular cells skipped and counted."""
+    from tests import _msa_ref
+    rows, skew = _degenerate_alignment()
+    seen = {k: 0 for k in (_msa_ref.REGULAR, _msa_ref.SPECIAL, _msa_ref.NEAR)}
+    for seqs in (rows, skew):
+        L = len(seqs[0])
+        P = orc.pack4_many(seqs)
+        got = orc.msa_dist_lower(P, L, dist_type)
+        cls, ref = _msa_ref.dist_lower(seqs, dist_type)
+        u, m = orc.msa_counts(P, L)
+        cs = [_msa_ref.codes(s) for s in seqs]
+        for r in range(1, len(seqs)):
+            for c in range(r):
+                k = _msa_ref.Counts(cs[r], cs[c])
+                assert (u[r, c], m[r, c]) == (k.useful, k.match), (r, c)
+                seen[cls[r, c]] += 1
+                g, e = got[r, c], ref[r, c]
+                if cls[r, c] == _msa_ref.REGULAR:
+                    assert abs(g - e) <= 1e-12 * abs(e), (r, c, g, e)
+                elif cls[r, c] == _msa_ref.SPECIAL:
+                    assert (np.isnan(g) and np.isnan(e)) or g == e, (r, c, g, e)
+    with capsys.disabled():
+        print(f"\n  type {dist_type}: {seen}")
+    assert seen[_msa_ref.REGULAR] >= 30 and seen[_msa_ref.SPECIAL] >= 1
+    assert seen[_msa_ref.NEAR] <= 2
