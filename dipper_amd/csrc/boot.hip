@@ -241,13 +241,12 @@ int dpr_comm_sum_i32(dpr_ctx* c, int32_t* host_inout, int64_t count)
     if (!c || count < 0 || (count > 0 && !host_inout)) { set_error("dpr_comm_sum_i32: bad argument"); return DPR_ERR_ARG; }
     if (c->world <= 1 || c->vworld > 0 || count == 0) return DPR_OK;     // one rank (or all of them in this context)
     DPR_HIP(hipSetDevice(c->device));
-    int32_t* d = nullptr;
-    DPR_HIP(hipMalloc(&d, sizeof(int32_t) * (size_t)count));
+    DevBuf<int32_t> d;
+    DPR_HIP(d.alloc((size_t)count));
     int rc = hipMemcpyAsync(d, host_inout, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, c->stream) == hipSuccess ? DPR_OK : DPR_ERR_HIP;
     if (rc == DPR_OK) rc = comm_all_reduce_sum(c, d, (size_t)count, kNcclInt32, c->stream);
     if (rc == DPR_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = DPR_ERR_HIP;
     if (rc == DPR_OK && hipMemcpy(host_inout, d, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost) != hipSuccess) rc = DPR_ERR_HIP;
-    (void)hipFree(d);
     if (rc == DPR_ERR_HIP) { (void)hipGetLastError(); set_error("dpr_comm_sum_i32: HIP error"); }
     return rc;
 }

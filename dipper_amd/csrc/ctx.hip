@@ -253,15 +253,12 @@ int dpr_get_kmer_hashes(dpr_ctx* c, int64_t seq, int k, const uint64_t* word_off
     const uint64_t L = len[seq];
     if (L < (uint64_t)k) return DPR_OK;
     const uint64_t nk = L - (uint64_t)k + 1;
-    uint64_t* d = nullptr;
-    DPR_HIP(hipMalloc(&d, sizeof(uint64_t) * nk));
-    int rc = mash_hash_positions(c->mash, seq, k, d, L, word_off[seq], c->stream);
-    if (rc == DPR_OK) {
-        DPR_HIP(hipStreamSynchronize(c->stream));
-        DPR_HIP(hipMemcpy(out, d, sizeof(uint64_t) * nk, hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d);
-    return rc;
+    DevBuf<uint64_t> d;
+    DPR_HIP(d.alloc(nk));
+    if (int rc = mash_hash_positions(c->mash, seq, k, d, L, word_off[seq], c->stream)) return rc;
+    DPR_HIP(hipStreamSynchronize(c->stream));
+    DPR_HIP(hipMemcpy(out, d, sizeof(uint64_t) * nk, hipMemcpyDeviceToHost));
+    return DPR_OK;
 }
 
 // microbenchmark: wall time per launch of a chain of trivial dependent kernels (eager or graph replay)
@@ -273,45 +270,42 @@ int dpr_launch_bench(dpr_ctx* c, int nlaunch, int grid, int use_graph, float* us
 {
     if (!c || nlaunch < 1 || grid < 1 || !us_per_launch) { set_error("dpr_launch_bench: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    unsigned long long* buf = nullptr;
-    DPR_HIP(hipMalloc(&buf, 64));
+    DevBuf<unsigned long long> buf;
+    DPR_HIP(buf.alloc(8));
     DPR_HIP(hipMemset(buf, 0, 64));
-    hipGraphExec_t ge = nullptr;
+    ScopedGraph g_keep;       // use_graph == 2 (the node handles live in the graph: it stays until the replays are done)
+    ScopedGraphExec ge;
     const int per = 128;
     if (use_graph) {
-        hipGraph_t g = nullptr;
+        ScopedGraph g;
         DPR_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         for (int k = 0; k < per; ++k) hipLaunchKernelGGL(dpr_nop_kernel, dim3(grid), dim3(256), 0, c->stream, buf);
-        DPR_HIP(hipStreamEndCapture(c->stream, &g));
-        DPR_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        DPR_HIP(hipGraphDestroy(g));
+        DPR_HIP(hipStreamEndCapture(c->stream, g.put()));
+        DPR_HIP(hipGraphInstantiate(ge.put(), g, nullptr, nullptr, 0));
     }
     // use_graph == 2: an explicitly built chain whose nodes get NEW PARAMETERS (argument and grid) before every replay --
     // what a loop with per-launch arguments (placement: the tip index, the distance row) would have to do to be replayed
     std::vector<hipGraphNode_t> nodes;
-    hipGraph_t g_keep = nullptr;
-    unsigned long long* marks = nullptr;          // use_graph == 2: launch i writes marks[i] = i + 1 (every launch must see ITS parameters)
+    DevBuf<unsigned long long> marks;             // use_graph == 2: launch i writes marks[i] = i + 1 (every launch must see ITS parameters)
     if (use_graph == 2) {
-        DPR_HIP(hipMalloc(&marks, sizeof(unsigned long long) * (size_t)nlaunch));
+        DPR_HIP(marks.alloc((size_t)nlaunch));
         DPR_HIP(hipMemset(marks, 0, sizeof(unsigned long long) * (size_t)nlaunch));
     }
     unsigned long long* argp = marks;
     long long argi = 0;
     void* kargs[2] = { &argp, &argi };
     if (use_graph == 2) {
-        if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
-        hipGraph_t g = nullptr;
-        DPR_HIP(hipGraphCreate(&g, 0));
+        ge.reset();
+        DPR_HIP(hipGraphCreate(g_keep.put(), 0));
         for (int k = 0; k < per; ++k) {
             hipKernelNodeParams kp{};
             kp.func = reinterpret_cast<void*>(dpr_mark_kernel);
             kp.gridDim = dim3((unsigned)grid); kp.blockDim = dim3(256); kp.sharedMemBytes = 0; kp.kernelParams = kargs; kp.extra = nullptr;
             hipGraphNode_t nd = nullptr;
-            DPR_HIP(hipGraphAddKernelNode(&nd, g, k ? &nodes.back() : nullptr, k ? 1 : 0, &kp));
+            DPR_HIP(hipGraphAddKernelNode(&nd, g_keep, k ? &nodes.back() : nullptr, k ? 1 : 0, &kp));
             nodes.push_back(nd);
         }
-        DPR_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-        g_keep = g;       // (the node handles live in the graph: it stays until the replays are done)
+        DPR_HIP(hipGraphInstantiate(ge.put(), g_keep, nullptr, nullptr, 0));
     }
     DPR_HIP(hipStreamSynchronize(c->stream));
     DPR_HIP(hipEventRecord(c->ev[2], c->stream));
@@ -342,11 +336,7 @@ int dpr_launch_bench(dpr_ctx* c, int nlaunch, int grid, int use_graph, float* us
             for (long long i = 0; i < done; ++i) bad += h[(size_t)i] != (unsigned long long)i + 1ull;
             if (bad) { set_error("dpr_launch_bench: " + std::to_string(bad) + " of " + std::to_string(done) + " replayed launches did not run with their own parameters"); rc_marks = DPR_ERR_STATE; }
         }
-        (void)hipFree(marks);
     }
-    if (ge) (void)hipGraphExecDestroy(ge);
-    if (g_keep) (void)hipGraphDestroy(g_keep);
-    (void)hipFree(buf);
     return rc_marks;
 }
 
@@ -482,17 +472,14 @@ int dpr_get_msa_counts(dpr_ctx* c, int64_t row, int32_t* useful, int32_t* match)
 {
     if (!c || !c->msa.planes || row < 0 || row >= c->msa.n) { set_error("dpr_get_msa_counts: bad argument"); return DPR_ERR_ARG; }
     if (row == 0) return DPR_OK;
-    int32_t *du = nullptr, *dm = nullptr;
-    DPR_HIP(hipMalloc(&du, sizeof(int32_t) * (size_t)row));
-    DPR_HIP(hipMalloc(&dm, sizeof(int32_t) * (size_t)row));
-    int rc = msa_counts_row(c->msa, row, du, dm, c->stream);
-    if (rc == DPR_OK) {
-        DPR_HIP(hipStreamSynchronize(c->stream));
-        DPR_HIP(hipMemcpy(useful, du, sizeof(int32_t) * (size_t)row, hipMemcpyDeviceToHost));
-        DPR_HIP(hipMemcpy(match, dm, sizeof(int32_t) * (size_t)row, hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(du); (void)hipFree(dm);
-    return rc;
+    DevBuf<int32_t> du, dm;
+    DPR_HIP(du.alloc((size_t)row));
+    DPR_HIP(dm.alloc((size_t)row));
+    if (int rc = msa_counts_row(c->msa, row, du, dm, c->stream)) return rc;
+    DPR_HIP(hipStreamSynchronize(c->stream));
+    DPR_HIP(hipMemcpy(useful, du, sizeof(int32_t) * (size_t)row, hipMemcpyDeviceToHost));
+    DPR_HIP(hipMemcpy(match, dm, sizeof(int32_t) * (size_t)row, hipMemcpyDeviceToHost));
+    return DPR_OK;
 }
 
 // test / measurement hook: the distance block of tips [row0, row0 + nrows) against tips [0, ncols) through the launcher the
@@ -503,12 +490,12 @@ int dpr_msa_dist_block(dpr_ctx* c, int64_t row0, int64_t nrows, int64_t ncols, i
 {
     if (!c || !c->msa.planes || row0 < 0 || nrows < 1 || row0 + nrows > c->msa.n || ncols < 1 || ncols > c->msa.n || reps < 1) { set_error("dpr_msa_dist_block: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    double* d = nullptr;
+    DevBuf<double> d;
     const int64_t ld = transposed ? nrows : ncols;
-    DPR_HIP(hipMalloc(&d, sizeof(double) * (size_t)(nrows * ncols)));
+    DPR_HIP(d.alloc((size_t)(nrows * ncols)));
     int rc = msa_dist_block_rows(c->msa, row0, nrows, 0, 0, ncols, dist_type, d, ld, c->stream, transposed != 0);      // warm
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (rc == DPR_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = DPR_ERR_HIP;
+    ScopedEvent e0, e1;
+    if (rc == DPR_OK && (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess)) rc = DPR_ERR_HIP;
     if (rc == DPR_OK) {
         (void)hipEventRecord(e0, c->stream);
         for (int r = 0; r < reps && rc == DPR_OK; ++r) rc = msa_dist_block_rows(c->msa, row0, nrows, 0, 0, ncols, dist_type, d, ld, c->stream, transposed != 0);
@@ -519,9 +506,6 @@ int dpr_msa_dist_block(dpr_ctx* c, int64_t row0, int64_t nrows, int64_t ncols, i
     if (rc == DPR_OK) (void)hipEventElapsedTime(&ms, e0, e1);
     if (ms_avg) *ms_avg = ms / (float)reps;
     if (rc == DPR_OK && out && hipMemcpy(out, d, sizeof(double) * (size_t)(nrows * ncols), hipMemcpyDeviceToHost) != hipSuccess) rc = DPR_ERR_HIP;
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d);
     if (rc == DPR_ERR_HIP) { (void)hipGetLastError(); set_error("dpr_msa_dist_block: HIP error"); }
     return rc;
 }

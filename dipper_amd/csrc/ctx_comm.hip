@@ -445,11 +445,12 @@ int dpr_comm_selftest(dpr_ctx* c)
     r = g_rccl.CommInitRank(&comm, 1, id, 0);
     if (r != 0) { set_error(std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?")); return DPR_ERR_COMM; }
     NjRecord h{ -1.5, 42ull, 2.25, 7ull }, back{ 0, 0, 0, 0 };
-    NjRecord* d = nullptr;
-    double *ds = nullptr, *dg = nullptr;
-    DPR_HIP(hipMalloc(&d, sizeof(NjRecord)));
-    DPR_HIP(hipMalloc(&ds, sizeof(double) * 192));
-    DPR_HIP(hipMalloc(&dg, sizeof(double) * 192));
+    struct CommGuard { void* comm; ~CommGuard() { g_rccl.CommDestroy(comm); } } comm_guard{ comm };
+    DevBuf<NjRecord> d;
+    DevBuf<double> ds, dg;
+    DPR_HIP(d.alloc(1));
+    DPR_HIP(ds.alloc(192));
+    DPR_HIP(dg.alloc(192));
     std::vector<double> hs(192), hg(192, 0.0);
     for (int i = 0; i < 192; ++i) hs[(size_t)i] = 0.5 * i;
     DPR_HIP(hipMemcpy(d, &h, sizeof(NjRecord), hipMemcpyHostToDevice));
@@ -465,8 +466,6 @@ int dpr_comm_selftest(dpr_ctx* c)
     DPR_HIP(hipMemcpy(hr.data(), ds, sizeof(double) * 192, hipMemcpyDeviceToHost));
     DPR_HIP(hipMemcpy(&back, d, sizeof(NjRecord), hipMemcpyDeviceToHost));
     DPR_HIP(hipMemcpy(hg.data(), dg, sizeof(double) * 192, hipMemcpyDeviceToHost));
-    (void)hipFree(d); (void)hipFree(ds); (void)hipFree(dg);
-    g_rccl.CommDestroy(comm);
     if (r != 0) { set_error("ncclAllGather / ncclAllReduce failed"); return DPR_ERR_COMM; }
     if (back.q != h.q || back.key != h.key || back.d != h.d || hg != hs || hr != hs) { set_error("dpr_comm_selftest: data mismatch"); return DPR_ERR_COMM; }
     return DPR_OK;

@@ -253,27 +253,25 @@ int dpr_warm_graphs(dpr_ctx* c)
 {
     if (!c) { set_error("dpr_warm_graphs: null ctx"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    hipStream_t st = nullptr;
-    DPR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
+    ScopedStream st;
+    DPR_HIP(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         hipLaunchKernelGGL(dpr_warm_kernel, dim3(1), dim3(64), 0, st, 0);
-        if (hipStreamEndCapture(st, &g) == hipSuccess && g) {
-            if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess && ge) {
+        ScopedGraph g;
+        ScopedGraphExec ge;
+        if (hipStreamEndCapture(st, g.put()) == hipSuccess && g) {
+            if (hipGraphInstantiate(ge.put(), g, nullptr, nullptr, 0) == hipSuccess && ge) {
                 (void)hipGraphLaunch(ge, st);
                 (void)hipStreamSynchronize(st);
-                (void)hipGraphExecDestroy(ge);
             }
-            (void)hipGraphDestroy(g);
         }
     }
     // ... and of its staged copies: the first device-to-host copy of more than a few KB into pageable memory costs 7.7 ms
     // (staging buffers); without this it is the first epoch rebuild of the NJ run that pays (240 KB of row sums)
     {
-        void* d = nullptr;
+        DevBuf<char> d;
         constexpr size_t kWarmBytes = 512 << 10;
-        if (hipMalloc(&d, kWarmBytes) == hipSuccess) {
+        if (d.alloc(kWarmBytes) == hipSuccess) {
             std::vector<char> h(kWarmBytes);
             (void)hipMemsetAsync(d, 0, kWarmBytes, st);
             (void)hipStreamSynchronize(st);
@@ -284,11 +282,9 @@ int dpr_warm_graphs(dpr_ctx* c)
             (void)hipStreamSynchronize(st);
             (void)hipMemcpyAsync(d, h.data(), kWarmBytes, hipMemcpyHostToDevice, st);
             (void)hipStreamSynchronize(st);
-            (void)hipFree(d);
         }
     }
     (void)hipGetLastError();
-    (void)hipStreamDestroy(st);
     return DPR_OK;
 }
 

@@ -4,6 +4,65 @@
 
 using namespace dpr;
 
+// ---- said once for the three tree builders --------------------------------------------------------------
+// is `source` set up for n tips?  `fn` is the entry point's name for the message (dpr_dc_run turns a matrix away before it asks)
+static int check_source(dpr_ctx* c, const char* fn, int source, int k, int64_t n)
+{
+    const std::string f(fn);
+    if (source == DPR_SRC_MSA) {
+        if (!c->msa.planes || c->msa.n != n) { set_error(f + ": call dpr_set_msa with n sequences first"); return DPR_ERR_STATE; }
+    } else if (source == DPR_SRC_MASH) {
+        if (!c->mash.sketches || c->mash.n != n) { set_error(f + ": call dpr_set_reads and dpr_sketch first"); return DPR_ERR_STATE; }
+        if (k != c->mash.k) { set_error(f + ": k differs from the sketch k"); return DPR_ERR_ARG; }
+    } else if (source == DPR_SRC_MATRIX) {
+        if (!c->packed_lower || c->n_input != n) { set_error(f + ": call dpr_set_matrix_lower first"); return DPR_ERR_STATE; }
+    } else { set_error(f + ": unknown source"); return DPR_ERR_ARG; }
+    return DPR_OK;
+}
+
+// c->place_trace: a fresh zeroed [3n] for this run
+static int reset_place_trace(dpr_ctx* c, int64_t n)
+{
+    if (c->place_trace) { (void)hipFree(c->place_trace); c->place_trace = nullptr; }
+    DPR_HIP(hipMalloc(&c->place_trace, sizeof(double) * (size_t)(3 * n)));
+    DPR_HIP(hipMemsetAsync(c->place_trace, 0, sizeof(double) * (size_t)(3 * n), c->stream));
+    return DPR_OK;
+}
+
+// the adjacency arrays head[2n] e[8n] nxt[8n] belong[8n] len[8n] between the caller and c->place, on c->stream
+static int copy_adjacency(dpr_ctx* c, int64_t n, bool to_device, int32_t* head, int32_t* e, int32_t* nxt, int32_t* belong, double* len)
+{
+    const PlaceBuffers& p = c->place;
+    struct Arr { void* host; void* dev; size_t bytes; };
+    const Arr arrs[] = { { head, p.head, sizeof(int32_t) * (size_t)(2 * n) }, { e, p.e, sizeof(int32_t) * (size_t)(8 * n) },
+                         { nxt, p.nxt, sizeof(int32_t) * (size_t)(8 * n) }, { belong, p.belong, sizeof(int32_t) * (size_t)(8 * n) },
+                         { len, p.len, sizeof(double) * (size_t)(8 * n) } };
+    for (const Arr& a : arrs) {
+        if (to_device) DPR_HIP(hipMemcpyAsync(a.dev, a.host, a.bytes, hipMemcpyHostToDevice, c->stream));
+        else DPR_HIP(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    return DPR_OK;
+}
+
+// distance rows of a source: MSA and Mash rows are computed into a buffer, the packed triangle is read in place
+struct RowSource {
+    dpr_ctx* c;
+    int source, dist_type;
+    // rows [i0, i0 + nr) x columns [0, ncols) into out (row stride ld; transposed: column stride ld)
+    int fill(int64_t i0, int64_t nr, double* out, int64_t ld, int64_t ncols, hipStream_t st, bool transposed = false) const
+    {
+        if (nr <= 0) return DPR_OK;
+        if (source == DPR_SRC_MSA) return msa_dist_block_rows(c->msa, i0, nr, 0, 0, ncols, dist_type, out, ld, st, transposed);
+        if (source == DPR_SRC_MASH) return mash_dist_rows(c->mash, i0, nr, 0, 0, false, ncols, out, ld, st, transposed);
+        return DPR_OK;
+    }
+    // row i of a buffer that starts at row i0 (row stride ld), or of the packed triangle
+    const double* row_ptr(int64_t i, int64_t i0, const double* rows, int64_t ld) const
+    {
+        return source == DPR_SRC_MATRIX ? c->packed_lower + i * (i - 1) / 2 : rows + (i - i0) * ld;
+    }
+};
+
 extern "C" {
 
 // k-closest placement of tips [first, last) into c->place (findPlacementTree / addQuery loop,
@@ -50,13 +109,12 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
     // (several ranks: every rank must take the same decisions -- the batches' all-gathers are enqueued on the stream the decision
     //  picks -- and a rank's share of a batch is 1 / G of the pairs, i.e. the short side: every batch beside, as in round 3)
     const bool overlap_always = overlap_allowed && sharded;
-    double* rows_buf[2] = { nullptr, nullptr };
-    const size_t row_bytes = sizeof(double) * (size_t)(per * W * ldb);
+    DevBuf<double> rows_buf[2];
     if (source != DPR_SRC_MATRIX) {
-        DPR_HIP(hipMalloc(&rows_buf[0], row_bytes));
+        DPR_HIP(rows_buf[0].alloc((size_t)(per * W * ldb)));
         if (overlap_allowed) {
-            const hipError_t me = hipMalloc(&rows_buf[1], row_bytes);
-            if (me != hipSuccess) { (void)hipFree(rows_buf[0]); return hip_fail(me, "hipMalloc(second row buffer)"); }
+            const hipError_t me = rows_buf[1].alloc((size_t)(per * W * ldb));
+            if (me != hipSuccess) return hip_fail(me, "hipMalloc(second row buffer)");
         }
     }
     if (overlap_allowed && !c->stream2) {
@@ -66,17 +124,10 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
         DPR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         DPR_HIP(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least));
     }
-    std::vector<hipEvent_t> sync_ev;                             // fill-done / tree-done events of this run
-    auto new_event = [&](hipEvent_t* e) -> int { DPR_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming)); sync_ev.push_back(*e); return DPR_OK; };
-    auto row_ptr = [&](int64_t i, int64_t i0, const double* rows) -> const double* {
-        return source == DPR_SRC_MATRIX ? c->packed_lower + i * (i - 1) / 2 : rows + (i - i0) * ldb;
-    };
-    auto fill_some = [&](int64_t i0, int64_t nr, double* out, hipStream_t st) -> int {
-        if (nr <= 0) return DPR_OK;
-        if (source == DPR_SRC_MSA) return msa_dist_block_rows(c->msa, i0, nr, 0, 0, i0 + nr, dist_type, out, ldb, st);
-        if (source == DPR_SRC_MASH) return mash_dist_rows(c->mash, i0, nr, 0, 0, false, i0 + nr, out, ldb, st);
-        return DPR_OK;
-    };
+    std::vector<ScopedEvent> sync_ev;                            // fill-done / tree-done events of this run
+    auto new_event = [&](hipEvent_t* e) -> int { sync_ev.emplace_back(); DPR_HIP(hipEventCreateWithFlags(sync_ev.back().put(), hipEventDisableTiming)); *e = sync_ev.back(); return DPR_OK; };
+    const RowSource src{ c, source, dist_type };
+    auto fill_some = [&](int64_t i0, int64_t nr, double* out, hipStream_t st) -> int { return src.fill(i0, nr, out, ldb, i0 + nr, st); };
     auto fill_rows_inner = [&](int64_t i0, int64_t nr, double* rows, hipStream_t ds) -> int {
         if (!sharded) return fill_some(i0, nr, rows, ds);
         const int64_t a = (int64_t)c->rank * per, b = a + per < nr ? a + per : nr;     // this rank's rows of the batch
@@ -94,9 +145,9 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
         hipStream_t ds = beside ? c->stream2 : c->stream;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (source != DPR_SRC_MATRIX) {
-            DPR_HIP(hipEventCreate(&e0)); DPR_HIP(hipEventCreate(&e1));
-            std::vector<hipEvent_t>& dst = beside ? c->place_ev_busy : c->place_ev;
-            dst.push_back(e0); dst.push_back(e1);
+            std::vector<hipEvent_t>& dst = beside ? c->place_ev_busy : c->place_ev;      // (handed over one by one: nothing is lost if the second create fails)
+            DPR_HIP(hipEventCreate(&e0)); dst.push_back(e0);
+            DPR_HIP(hipEventCreate(&e1)); dst.push_back(e1);
             DPR_HIP(hipEventRecord(e0, ds));
         }
         c->mash.share_chip = beside;
@@ -111,7 +162,7 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
         if (first == 2) {
             if (int rc = place_init_fresh(p, c->stream)) return rc;
             if (int rc = fill_some(1, 1, rows_buf[0], c->stream)) return rc;
-            if (int rc = place_initial_tree(p, row_ptr(1, 1, rows_buf[0]), c->stream)) return rc;
+            if (int rc = place_initial_tree(p, src.row_ptr(1, 1, rows_buf[0], ldb), c->stream)) return rc;
         } else {
             if (int rc = place_import_backbone(p, first, c->stream)) return rc;
         }
@@ -152,8 +203,8 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
                 pr.dist_alone = true;
             } else {
                 hipEvent_t w0 = nullptr, w1 = nullptr;
-                DPR_HIP(hipEventCreate(&w0)); DPR_HIP(hipEventCreate(&w1));
-                c->place_ev.push_back(w0); c->place_ev.push_back(w1);
+                DPR_HIP(hipEventCreate(&w0)); c->place_ev.push_back(w0);
+                DPR_HIP(hipEventCreate(&w1)); c->place_ev.push_back(w1);
                 DPR_HIP(hipEventRecord(w0, c->stream));
                 DPR_HIP(hipStreamWaitEvent(c->stream, filled[cur], 0));
                 DPR_HIP(hipEventRecord(w1, c->stream));
@@ -189,13 +240,13 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
                 }
             }
             if (source != DPR_SRC_MATRIX) {
-                DPR_HIP(hipEventCreate(&pr.t0)); DPR_HIP(hipEventCreate(&pr.t1));
-                c->place_ev_tree.push_back(pr.t0); c->place_ev_tree.push_back(pr.t1);
+                DPR_HIP(hipEventCreate(&pr.t0)); c->place_ev_tree.push_back(pr.t0);
+                DPR_HIP(hipEventCreate(&pr.t1)); c->place_ev_tree.push_back(pr.t1);
                 DPR_HIP(hipEventRecord(pr.t0, c->stream));
             }
             if (source == DPR_SRC_MATRIX) {      // packed triangle: rows are not evenly spaced
                 for (int64_t i = i0; i < i0 + nr; ++i)
-                    if (int rc = place_tip(p, row_ptr(i, i0, rows), i, c->place_trace, c->stream)) return rc;
+                    if (int rc = place_tip(p, src.row_ptr(i, i0, rows, ldb), i, c->place_trace, c->stream)) return rc;
             } else {
                 if (int rc = place_tips(p, rows, ldb, i0, nr, c->place_trace, c->stream)) return rc;
             }
@@ -208,12 +259,10 @@ static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int
     };
     const int rc = run();
     c->mash.share_chip = false;
-    if (rows_buf[0] || rows_buf[1]) {
+    if (rows_buf[0] || rows_buf[1]) {     // both streams are done with the row buffers before the scope releases them
         (void)hipStreamSynchronize(c->stream);
         if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-        for (double* q : rows_buf) if (q) (void)hipFree(q);
     }
-    for (hipEvent_t e : sync_ev) (void)hipEventDestroy(e);
     return rc;
 }
 
@@ -270,14 +319,7 @@ int dpr_place_run(dpr_ctx* c, int source, int dist_type, int k, int64_t first, i
 {
     if (!c || !head || !e || !nxt || !belong || !len || n < 3 || first < 2 || first > n) { set_error("dpr_place_run: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    if (source == DPR_SRC_MSA) {
-        if (!c->msa.planes || c->msa.n != n) { set_error("dpr_place_run: call dpr_set_msa with n sequences first"); return DPR_ERR_STATE; }
-    } else if (source == DPR_SRC_MASH) {
-        if (!c->mash.sketches || c->mash.n != n) { set_error("dpr_place_run: call dpr_set_reads and dpr_sketch first"); return DPR_ERR_STATE; }
-        if (k != c->mash.k) { set_error("dpr_place_run: k differs from the sketch k"); return DPR_ERR_ARG; }
-    } else if (source == DPR_SRC_MATRIX) {
-        if (!c->packed_lower || c->n_input != n) { set_error("dpr_place_run: call dpr_set_matrix_lower first"); return DPR_ERR_STATE; }
-    } else { set_error("dpr_place_run: unknown source"); return DPR_ERR_ARG; }
+    if (int rc = check_source(c, "dpr_place_run", source, k, n)) return rc;
     if (first > 2) {
         // An imported backbone must be a rooted binary tree: `first` tips, first - 1 internal nodes, 2 first - 2 edges = the slots
         // [0, 4 first - 4) all in use.  The reference's scan reads head[e[slot]] of every slot below 4 num - 4
@@ -293,25 +335,13 @@ int dpr_place_run(dpr_ctx* c, int source, int dist_type, int k, int64_t first, i
     }
     if (int rc = place_alloc(c->place, n)) return rc;
     PlaceBuffers& p = c->place;
-    if (c->place_trace) { (void)hipFree(c->place_trace); c->place_trace = nullptr; }
-    DPR_HIP(hipMalloc(&c->place_trace, sizeof(double) * (size_t)(3 * n)));
-    DPR_HIP(hipMemsetAsync(c->place_trace, 0, sizeof(double) * (size_t)(3 * n), c->stream));
+    if (int rc = reset_place_trace(c, n)) return rc;
     DPR_HIP(hipMemsetAsync(p.misc + 2, 0, 2 * sizeof(int32_t), c->stream));      // fallback counters of the four-tip launches (dpr_get_place_walks)
-    if (first > 2) {
-        DPR_HIP(hipMemcpyAsync(p.head, head, sizeof(int32_t) * (size_t)(2 * n), hipMemcpyHostToDevice, c->stream));
-        DPR_HIP(hipMemcpyAsync(p.e, e, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyHostToDevice, c->stream));
-        DPR_HIP(hipMemcpyAsync(p.nxt, nxt, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyHostToDevice, c->stream));
-        DPR_HIP(hipMemcpyAsync(p.belong, belong, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyHostToDevice, c->stream));
-        DPR_HIP(hipMemcpyAsync(p.len, len, sizeof(double) * (size_t)(8 * n), hipMemcpyHostToDevice, c->stream));
-    }
+    if (first > 2) { if (int rc = copy_adjacency(c, n, true, head, e, nxt, belong, len)) return rc; }
     DPR_HIP(hipEventRecord(c->ev[2], c->stream));
     if (int rc = place_range(c, source, dist_type, first, n)) { place_collect_dist_ms(c); return rc; }
     DPR_HIP(hipEventRecord(c->ev[3], c->stream));
-    DPR_HIP(hipMemcpyAsync(head, p.head, sizeof(int32_t) * (size_t)(2 * n), hipMemcpyDeviceToHost, c->stream));
-    DPR_HIP(hipMemcpyAsync(e, p.e, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-    DPR_HIP(hipMemcpyAsync(nxt, p.nxt, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-    DPR_HIP(hipMemcpyAsync(belong, p.belong, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-    DPR_HIP(hipMemcpyAsync(len, p.len, sizeof(double) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = copy_adjacency(c, n, false, head, e, nxt, belong, len)) return rc;
     DPR_HIP(hipStreamSynchronize(c->stream));
     float ms = 0;
     DPR_HIP(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
@@ -333,42 +363,27 @@ static int place_exact_attempt(dpr_ctx* c, int source, int dist_type, int k, int
 {
     if (!c || !head || !e || !nxt || !belong || !len || n < 3) { set_error("dpr_place_exact_run: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    if (source == DPR_SRC_MSA) {
-        if (!c->msa.planes || c->msa.n != n) { set_error("dpr_place_exact_run: call dpr_set_msa with n sequences first"); return DPR_ERR_STATE; }
-    } else if (source == DPR_SRC_MASH) {
-        if (!c->mash.sketches || c->mash.n != n) { set_error("dpr_place_exact_run: call dpr_set_reads and dpr_sketch first"); return DPR_ERR_STATE; }
-        if (k != c->mash.k) { set_error("dpr_place_exact_run: k differs from the sketch k"); return DPR_ERR_ARG; }
-    } else if (source == DPR_SRC_MATRIX) {
-        if (!c->packed_lower || c->n_input != n) { set_error("dpr_place_exact_run: call dpr_set_matrix_lower first"); return DPR_ERR_STATE; }
-    } else { set_error("dpr_place_exact_run: unknown source"); return DPR_ERR_ARG; }
+    if (int rc = check_source(c, "dpr_place_exact_run", source, k, n)) return rc;
     if (int rc = place_alloc(c->place, n)) return rc;
     if (int rc = exact_alloc(c->exact, n)) return rc;
     PlaceBuffers& p = c->place;
     ExactBuffers& x = c->exact;
-    if (c->place_trace) { (void)hipFree(c->place_trace); c->place_trace = nullptr; }
-    DPR_HIP(hipMalloc(&c->place_trace, sizeof(double) * (size_t)(3 * n)));
-    DPR_HIP(hipMemsetAsync(c->place_trace, 0, sizeof(double) * (size_t)(3 * n), c->stream));
+    if (int rc = reset_place_trace(c, n)) return rc;
     // distance rows in batches of R+1: the step of tip i also runs the passes of tip i+1, so a batch
     // shares its last row with the next one
     const int64_t R = 256;
     const int64_t ldb = (n + 15) / 16 * 16;
-    double* rows = nullptr;
-    if (source != DPR_SRC_MATRIX) DPR_HIP(hipMalloc(&rows, sizeof(double) * (size_t)((R + 1) * ldb)));
+    DevBuf<double> rows;
+    if (source != DPR_SRC_MATRIX) DPR_HIP(rows.alloc((size_t)((R + 1) * ldb)));
     int64_t r0 = 1;
-    auto row_ptr = [&](int64_t i) -> const double* {
-        return source == DPR_SRC_MATRIX ? c->packed_lower + i * (i - 1) / 2 : rows + (i - r0) * ldb;
-    };
-    auto fill_rows = [&](int64_t i0, int64_t nr) -> int {
-        if (source == DPR_SRC_MSA) return msa_dist_block_rows(c->msa, i0, nr, 0, 0, i0 + nr, dist_type, rows, ldb, c->stream);
-        if (source == DPR_SRC_MASH) return mash_dist_rows(c->mash, i0, nr, 0, 0, false, i0 + nr, rows, ldb, c->stream);
-        return DPR_OK;
-    };
+    const RowSource src{ c, source, dist_type };
+    auto row_ptr = [&](int64_t i) { return src.row_ptr(i, r0, rows, ldb); };
     DPR_HIP(hipEventRecord(c->ev[2], c->stream));
     int rc = DPR_OK;
     while (!rc) {
         const int64_t nr = n - r0 < R + 1 ? n - r0 : R + 1;
         if (r0 > 1) rc = exact_adapt(x, c->stream);
-        if (!rc) rc = fill_rows(r0, nr);
+        if (!rc) rc = src.fill(r0, nr, rows, ldb, r0 + nr, c->stream);
         if (!rc && r0 == 1) rc = exact_init(p, x, row_ptr(1), nr > 1 ? row_ptr(2) : nullptr, nr > 1, c->stream);
         for (int64_t i = r0 < 2 ? 2 : r0; !rc && i < r0 + nr - 1; ++i) rc = exact_tip(p, x, i, row_ptr(i + 1), true, c->place_trace, c->stream);
         if (rc) break;
@@ -377,14 +392,9 @@ static int place_exact_attempt(dpr_ctx* c, int source, int dist_type, int k, int
     }
     if (!rc) {
         DPR_HIP(hipEventRecord(c->ev[3], c->stream));
-        DPR_HIP(hipMemcpyAsync(head, p.head, sizeof(int32_t) * (size_t)(2 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(e, p.e, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(nxt, p.nxt, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(belong, p.belong, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(len, p.len, sizeof(double) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
+        rc = copy_adjacency(c, n, false, head, e, nxt, belong, len);
     }
-    const hipError_t se = hipStreamSynchronize(c->stream);
-    if (rows) (void)hipFree(rows);
+    const hipError_t se = hipStreamSynchronize(c->stream);     // (the stream is idle before the scope releases the rows)
     if (rc) return rc;
     DPR_HIP(se);
     float ms = 0;
@@ -429,28 +439,24 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
     if (!c || !head || !e || !nxt || !belong || !len || n < 4) { set_error("dpr_dc_run: bad argument"); return DPR_ERR_ARG; }
     if (backbone < 3 || backbone >= n) { set_error("dpr_dc_run: backbone size must be in [3, n)"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    if (source == DPR_SRC_MSA) {
-        if (!c->msa.planes || c->msa.n != n) { set_error("dpr_dc_run: call dpr_set_msa with n sequences first"); return DPR_ERR_STATE; }
-    } else if (source == DPR_SRC_MASH) {
-        if (!c->mash.sketches || c->mash.n != n) { set_error("dpr_dc_run: call dpr_set_reads and dpr_sketch first"); return DPR_ERR_STATE; }
-        if (k != c->mash.k) { set_error("dpr_dc_run: k differs from the sketch k"); return DPR_ERR_ARG; }
-    } else {
+    if (source != DPR_SRC_MSA && source != DPR_SRC_MASH) {
         // src/divide_and_conquer/placement_close_k.cu:969-972
         set_error("dpr_dc_run: input must be unaligned or aligned sequences for the clustering based approach");
         return DPR_ERR_ARG;
     }
+    if (int rc = check_source(c, "dpr_dc_run", source, k, n)) return rc;
     const int64_t B = backbone;
     if (int rc = place_alloc(c->place, n, B)) return rc;
     PlaceBuffers& p = c->place;
-    if (c->place_trace) { (void)hipFree(c->place_trace); c->place_trace = nullptr; }
-    DPR_HIP(hipMalloc(&c->place_trace, sizeof(double) * (size_t)(3 * n)));
-    DPR_HIP(hipMemsetAsync(c->place_trace, 0, sizeof(double) * (size_t)(3 * n), c->stream));
-    hipEvent_t ev[4];
-    for (auto& x : ev) DPR_HIP(hipEventCreate(&x));
-    int32_t* d_cl = nullptr;
-    double* dT = nullptr;
-    uint64_t *snap_old = nullptr, *snap_acc = nullptr;
+    if (int rc = reset_place_trace(c, n)) return rc;
+    ScopedEvent ev[4];
+    for (auto& x : ev) DPR_HIP(hipEventCreate(x.put()));
+    DevBuf<int32_t> d_cl;
+    DevBuf<double> dT;
+    DevBuf<uint64_t> snap_old, snap_acc;
     DcTable tab;
+    struct TableGuard { DcTable& t; ~TableGuard() { dc_table_free(t); } } tab_guard{ tab };
+    const RowSource src{ c, source, dist_type };
     // ranks: RCCL ranks of dpr_comm_init, or -- validation on one GPU -- DPR_DC_VIRTUAL_RANKS(w) emulated in turn
     const bool real = comm_real(c);
     const int W = real ? c->world : (((flags >> 8) & 0xff) > 1 ? ((flags >> 8) & 0xff) : 1);
@@ -469,8 +475,8 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
         if (Q > 8192) Q = 8192;
         const int64_t nq = n - B;
         if (Q > (nq + 255) / 256 * 256) Q = (nq + 255) / 256 * 256;
-        DPR_HIP(hipMalloc(&dT, sizeof(double) * (size_t)(B * Q)));
-        DPR_HIP(hipMalloc(&d_cl, sizeof(int32_t) * (size_t)(n + 1)));
+        DPR_HIP(dT.alloc((size_t)(B * Q)));
+        DPR_HIP(d_cl.alloc((size_t)(n + 1)));
         DPR_HIP(hipMemsetAsync(d_cl, 0, sizeof(int32_t) * (size_t)(n + 1), c->stream));
         // the reference's aligned-input kernel never writes the distance to backbone tip B-1
         // (src/divide_and_conquer/msa.cu:331 `idx>=ed-st`) and scans the 0.0 of a fresh allocation
@@ -481,10 +487,7 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
             dc_query_share(n, B, v, W, &q0, &q1);
             for (int64_t i0 = q0; i0 < q1; i0 += Q) {
                 const int64_t nr = q1 - i0 < Q ? q1 - i0 : Q;
-                int rc;
-                if (source == DPR_SRC_MSA) rc = msa_dist_block_rows(c->msa, i0, nr, 0, 0, B, dist_type, dT, Q, c->stream, true);
-                else rc = mash_dist_rows(c->mash, i0, nr, 0, 0, false, B, dT, Q, c->stream, true);
-                if (rc) return rc;
+                if (int rc = src.fill(i0, nr, dT, Q, B, c->stream, true)) return rc;
                 if (skip_last) DPR_HIP(hipMemsetAsync(dT + (B - 1) * Q, 0, sizeof(double) * (size_t)Q, c->stream));
                 if (int rc2 = dc_assign(tab, dT, Q, (int)nr, d_cl + i0, c->stream)) return rc2;
             }
@@ -496,7 +499,7 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
         DPR_HIP(hipEventRecord(ev[2], c->stream));
         DPR_HIP(hipStreamSynchronize(c->stream));
         for (int64_t t = 0; t < B; ++t) h_cl[(size_t)t] = -1;
-        (void)hipFree(dT); dT = nullptr;
+        dT.reset();                 // (before the budget below is read)
         // ---- cluster trees (findClusterTreeDC).  Multi-GPU: clusters are dealt to the ranks; an array element
         // is changed by at most one rank, so the states are merged as old + sum of (new - old) (dc_delta_*).
         size_t free_b = 0, total_b = 0;
@@ -512,8 +515,8 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
                                  { p.len, 8 * n }, { p.cid, 20 * n }, { p.cdis, 40 * n }, { c->place_trace, 3 * n } };
             int64_t tot = 0;
             for (const Arr& a : arrs) tot += a.words;
-            DPR_HIP(hipMalloc(&snap_old, sizeof(uint64_t) * (size_t)tot));
-            if (!real) { DPR_HIP(hipMalloc(&snap_acc, sizeof(uint64_t) * (size_t)tot)); DPR_HIP(hipMemsetAsync(snap_acc, 0, sizeof(uint64_t) * (size_t)tot, c->stream)); }
+            DPR_HIP(snap_old.alloc((size_t)tot));
+            if (!real) { DPR_HIP(snap_acc.alloc((size_t)tot)); DPR_HIP(hipMemsetAsync(snap_acc, 0, sizeof(uint64_t) * (size_t)tot, c->stream)); }
             int64_t off = 0;
             for (const Arr& a : arrs) { DPR_HIP(hipMemcpyAsync(snap_old + off, a.cur, sizeof(uint64_t) * (size_t)a.words, hipMemcpyDeviceToDevice, c->stream)); off += a.words; }
             if (budget > sizeof(uint64_t) * (size_t)tot * 2) budget -= sizeof(uint64_t) * (size_t)tot * 2;
@@ -544,11 +547,7 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
             }
         }
         DPR_HIP(hipEventRecord(ev[3], c->stream));
-        DPR_HIP(hipMemcpyAsync(head, p.head, sizeof(int32_t) * (size_t)(2 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(e, p.e, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(nxt, p.nxt, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(belong, p.belong, sizeof(int32_t) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipMemcpyAsync(len, p.len, sizeof(double) * (size_t)(8 * n), hipMemcpyDeviceToHost, c->stream));
+        if (int rc = copy_adjacency(c, n, false, head, e, nxt, belong, len)) return rc;
         DPR_HIP(hipStreamSynchronize(c->stream));
         float ms = 0;
         DPR_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); c->dc_ms[0] = ms;
@@ -560,12 +559,6 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
     };
     const int rc = run();
     place_collect_dist_ms(c);     // (backbone placement batches; the events must not outlive the run)
-    if (dT) (void)hipFree(dT);
-    if (d_cl) (void)hipFree(d_cl);
-    if (snap_old) (void)hipFree(snap_old);
-    if (snap_acc) (void)hipFree(snap_acc);
-    dc_table_free(tab);
-    for (auto& x : ev) (void)hipEventDestroy(x);
     return rc;
 }
 

@@ -283,8 +283,8 @@ int dc_table_build(PlaceBuffers& p, int64_t B, DcTable& t, hipStream_t s)
         DPR_HIP(hipMalloc(&t.ch_e0, sizeof(int32_t) * e0v.size()));
         DPR_HIP(hipMalloc(&t.ch_l0, sizeof(int32_t) * l0v.size()));
         DPR_HIP(hipMalloc(&t.ch_leaf, sizeof(int32_t) * leaf.size()));
-        int32_t* d_off = nullptr;
-        DPR_HIP(hipMalloc(&d_off, sizeof(int32_t) * off.size()));
+        DevBuf<int32_t> d_off;
+        DPR_HIP(d_off.alloc(off.size()));
         DPR_HIP(hipMalloc(&t.et_rec, sizeof(uint4) * vs.size() * kDcRec));
         DPR_HIP(hipMemcpy(t.ch_e0, e0v.data(), sizeof(int32_t) * e0v.size(), hipMemcpyHostToDevice));
         DPR_HIP(hipMemcpy(t.ch_l0, l0v.data(), sizeof(int32_t) * l0v.size(), hipMemcpyHostToDevice));
@@ -294,7 +294,7 @@ int dc_table_build(PlaceBuffers& p, int64_t B, DcTable& t, hipStream_t s)
                            t.vslots, t.nv, t.et_rec);
         DPR_HIP(hipGetLastError());
         DPR_HIP(hipStreamSynchronize(s));
-        (void)hipFree(d_off);
+        d_off.reset();
         if (log_level("dc") > 0)
             std::fprintf(stderr, "[dc] assignment table: %d entries in %d chunks (%.1f entries, %.1f distinct closest leaves per chunk), built in %.1f ms\n", t.nv, t.nch,
                          (double)t.nv / (double)t.nch, (double)leaf.size() / (double)t.nch,
@@ -668,17 +668,17 @@ int dc_cluster_phase(PlaceBuffers& p, const int32_t* h_cluster_id, int64_t N, in
     }
     if (ncl == 0) return DPR_OK;
 
-    int32_t *d_members = nullptr, *d_cols = nullptr, *d_clx = nullptr, *d_qid = nullptr, *d_qfrom = nullptr, *d_status = nullptr;
-    double* d_qdis = nullptr;
-    DcCluster* d_cl = nullptr;
-    DPR_HIP(hipMalloc(&d_members, sizeof(int32_t) * (size_t)nq));
-    DPR_HIP(hipMalloc(&d_cols, sizeof(int32_t) * (size_t)coff));
-    DPR_HIP(hipMalloc(&d_clx, sizeof(int32_t) * (size_t)(40 * N)));
-    DPR_HIP(hipMalloc(&d_qid, sizeof(int32_t) * (size_t)qoff));
-    DPR_HIP(hipMalloc(&d_qfrom, sizeof(int32_t) * (size_t)qoff));
-    DPR_HIP(hipMalloc(&d_qdis, sizeof(double) * (size_t)qoff));
-    DPR_HIP(hipMalloc(&d_status, sizeof(int32_t)));
-    DPR_HIP(hipMalloc(&d_cl, sizeof(DcCluster) * (size_t)ncl));
+    DevBuf<int32_t> d_members, d_cols, d_clx, d_qid, d_qfrom, d_status;
+    DevBuf<double> d_qdis;
+    DevBuf<DcCluster> d_cl;
+    DPR_HIP(d_members.alloc((size_t)nq));
+    DPR_HIP(d_cols.alloc((size_t)coff));
+    DPR_HIP(d_clx.alloc((size_t)(40 * N)));
+    DPR_HIP(d_qid.alloc((size_t)qoff));
+    DPR_HIP(d_qfrom.alloc((size_t)qoff));
+    DPR_HIP(d_qdis.alloc((size_t)qoff));
+    DPR_HIP(d_status.alloc(1));
+    DPR_HIP(d_cl.alloc((size_t)ncl));
     DPR_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     DPR_HIP(hipMemcpyAsync(d_members, members.data(), sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, s));
 
@@ -687,90 +687,73 @@ int dc_cluster_phase(PlaceBuffers& p, const int32_t* h_cluster_id, int64_t N, in
     std::vector<int64_t> h_moff, h_coff, h_out;
     std::vector<int32_t> h_m, h_ld;
     std::vector<int4> jobs;
-    int rc = DPR_OK;
-    int64_t g0 = 0;
-    int32_t* d_i32 = nullptr; int64_t* d_i64 = nullptr; int4* d_jobs = nullptr; double* d_out = nullptr;
-    auto cleanup_group = [&]() {
-        if (d_i32) (void)hipFree(d_i32);
-        if (d_i64) (void)hipFree(d_i64);
-        if (d_jobs) (void)hipFree(d_jobs);
-        if (d_out) (void)hipFree(d_out);
-        d_i32 = nullptr; d_i64 = nullptr; d_jobs = nullptr; d_out = nullptr;
-    };
     const int64_t big_m = 64;   // clusters above this size get a whole workgroup
-    auto run = [&]() -> int {
-        while (g0 < ncl) {
-            // ---- a group of clusters whose distance blocks fit the budget
-            int64_t g1 = g0, outsz = 0;
-            while (g1 < ncl) {
-                const int64_t add = (int64_t)cl[(size_t)g1].m * cl[(size_t)g1].ld;
-                if (g1 > g0 && (size_t)(outsz + add) * sizeof(double) > budget_bytes) break;
-                cl[(size_t)g1].out = outsz; outsz += add; ++g1;
-            }
-            const int64_t gn = g1 - g0;
-            h_moff.assign((size_t)gn, 0); h_coff.assign((size_t)gn, 0); h_out.assign((size_t)gn, 0);
-            h_m.assign((size_t)gn, 0); h_ld.assign((size_t)gn, 0);
-            jobs.clear();
-            for (int64_t i = 0; i < gn; ++i) {
-                const DcCluster& C = cl[(size_t)(g0 + i)];
-                h_moff[(size_t)i] = C.moff; h_coff[(size_t)i] = C.coff; h_out[(size_t)i] = C.out; h_m[(size_t)i] = C.m; h_ld[(size_t)i] = C.ld;
-                for (int t0 = 0; t0 < C.m; t0 += tr_rows) {
-                    const int tlast = std::min(C.m, t0 + tr_rows) - 1;
-                    const int ncol = kDcLeaves + tlast;               // positions u < 10 + t
-                    for (int u0 = 0; u0 < ncol; u0 += tr_cols) jobs.push_back(make_int4((int)i, t0, u0, 0));
-                }
-                if (stats) stats->pairs += (int64_t)C.m * kDcLeaves + (int64_t)C.m * (C.m - 1) / 2;
-            }
-            if (stats) { stats->groups++; stats->jobs += (int64_t)jobs.size(); }
-            DPR_HIP(hipMalloc(&d_i64, sizeof(int64_t) * (size_t)(3 * gn)));
-            DPR_HIP(hipMalloc(&d_i32, sizeof(int32_t) * (size_t)(2 * gn)));
-            DPR_HIP(hipMalloc(&d_jobs, sizeof(int4) * jobs.size()));
-            DPR_HIP(hipMalloc(&d_out, sizeof(double) * (size_t)(outsz > 0 ? outsz : 1)));
-            DPR_HIP(hipMemcpyAsync(d_i64, h_moff.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_i64 + gn, h_coff.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_i64 + 2 * gn, h_out.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_i32, h_m.data(), sizeof(int32_t) * (size_t)gn, hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_i32 + gn, h_ld.data(), sizeof(int32_t) * (size_t)gn, hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(int4) * jobs.size(), hipMemcpyHostToDevice, s));
-            DPR_HIP(hipMemcpyAsync(d_cl + g0, cl.data() + g0, sizeof(DcCluster) * (size_t)gn, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(dc_cols_kernel, dim3((unsigned)gn), dim3(64), 0, s, p, d_cl + g0, d_members, d_cols, d_clx);
-            PairJobs J;
-            J.jobs = d_jobs; J.members = d_members; J.cols = d_cols;
-            J.cl_moff = d_i64; J.cl_coff = d_i64 + gn; J.cl_out = d_i64 + 2 * gn;
-            J.cl_m = d_i32; J.cl_ld = d_i32 + gn; J.out = d_out;
-            if (source == DPR_SRC_MSA) { if (int r2 = msa_dist_jobs(*msa, dist_type, J, (int)jobs.size(), s)) return r2; }
-            else { if (int r2 = mash_dist_jobs(*mash, J, (int)jobs.size(), s)) return r2; }
-            // clusters are sorted by size: the large ones of the group first, a workgroup of 16 wavefronts each
-            int64_t nbig = 0;
-            while (nbig < gn && cl[(size_t)(g0 + nbig)].m > big_m) ++nbig;
-            if (nbig > 0) {
-                hipLaunchKernelGGL(dc_cluster_kernel<16>, dim3((unsigned)nbig), dim3(1024), 0, s, p, d_clx, d_cl + g0, d_members, d_out,
-                                   d_qid, d_qfrom, d_qdis, d_status, d_trace);
-                DPR_HIP(hipGetLastError());
-            }
-            if (gn > nbig) {
-                hipLaunchKernelGGL(dc_cluster_kernel<1>, dim3((unsigned)(gn - nbig)), dim3(64), 0, s, p, d_clx, d_cl + g0 + nbig, d_members, d_out,
-                                   d_qid, d_qfrom, d_qdis, d_status, d_trace);
-                DPR_HIP(hipGetLastError());
-            }
-            DPR_HIP(hipStreamSynchronize(s));   // host vectors and group buffers are reused
-            cleanup_group();
-            g0 = g1;
+    int64_t g0 = 0;
+    while (g0 < ncl) {
+        // ---- a group of clusters whose distance blocks fit the budget
+        int64_t g1 = g0, outsz = 0;
+        while (g1 < ncl) {
+            const int64_t add = (int64_t)cl[(size_t)g1].m * cl[(size_t)g1].ld;
+            if (g1 > g0 && (size_t)(outsz + add) * sizeof(double) > budget_bytes) break;
+            cl[(size_t)g1].out = outsz; outsz += add; ++g1;
         }
-        int32_t st = 0;
-        DPR_HIP(hipMemcpy(&st, d_status, sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (st != 0) {
-            set_error("divide-and-conquer: no eligible edge with pendant length < 2 in a cluster (distances >= 2?)");
-            return DPR_ERR_NOCAND;
+        const int64_t gn = g1 - g0;
+        h_moff.assign((size_t)gn, 0); h_coff.assign((size_t)gn, 0); h_out.assign((size_t)gn, 0);
+        h_m.assign((size_t)gn, 0); h_ld.assign((size_t)gn, 0);
+        jobs.clear();
+        for (int64_t i = 0; i < gn; ++i) {
+            const DcCluster& C = cl[(size_t)(g0 + i)];
+            h_moff[(size_t)i] = C.moff; h_coff[(size_t)i] = C.coff; h_out[(size_t)i] = C.out; h_m[(size_t)i] = C.m; h_ld[(size_t)i] = C.ld;
+            for (int t0 = 0; t0 < C.m; t0 += tr_rows) {
+                const int tlast = std::min(C.m, t0 + tr_rows) - 1;
+                const int ncol = kDcLeaves + tlast;               // positions u < 10 + t
+                for (int u0 = 0; u0 < ncol; u0 += tr_cols) jobs.push_back(make_int4((int)i, t0, u0, 0));
+            }
+            if (stats) stats->pairs += (int64_t)C.m * kDcLeaves + (int64_t)C.m * (C.m - 1) / 2;
         }
-        return DPR_OK;
-    };
-    rc = run();
-    cleanup_group();
-    void* ptrs[] = { d_members, d_cols, d_clx, d_qid, d_qfrom, d_qdis, d_status, d_cl };
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    return rc;
+        if (stats) { stats->groups++; stats->jobs += (int64_t)jobs.size(); }
+        DevBuf<int64_t> d_i64; DevBuf<int32_t> d_i32; DevBuf<int4> d_jobs; DevBuf<double> d_out;      // the group's buffers: released at the end of every group
+        DPR_HIP(d_i64.alloc((size_t)(3 * gn)));
+        DPR_HIP(d_i32.alloc((size_t)(2 * gn)));
+        DPR_HIP(d_jobs.alloc(jobs.size()));
+        DPR_HIP(d_out.alloc((size_t)(outsz > 0 ? outsz : 1)));
+        DPR_HIP(hipMemcpyAsync(d_i64, h_moff.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_i64 + gn, h_coff.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_i64 + 2 * gn, h_out.data(), sizeof(int64_t) * (size_t)gn, hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_i32, h_m.data(), sizeof(int32_t) * (size_t)gn, hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_i32 + gn, h_ld.data(), sizeof(int32_t) * (size_t)gn, hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(int4) * jobs.size(), hipMemcpyHostToDevice, s));
+        DPR_HIP(hipMemcpyAsync(d_cl + g0, cl.data() + g0, sizeof(DcCluster) * (size_t)gn, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(dc_cols_kernel, dim3((unsigned)gn), dim3(64), 0, s, p, d_cl + g0, d_members, d_cols, d_clx);
+        PairJobs J;
+        J.jobs = d_jobs; J.members = d_members; J.cols = d_cols;
+        J.cl_moff = d_i64; J.cl_coff = d_i64 + gn; J.cl_out = d_i64 + 2 * gn;
+        J.cl_m = d_i32; J.cl_ld = d_i32 + gn; J.out = d_out;
+        if (source == DPR_SRC_MSA) { if (int r2 = msa_dist_jobs(*msa, dist_type, J, (int)jobs.size(), s)) return r2; }
+        else { if (int r2 = mash_dist_jobs(*mash, J, (int)jobs.size(), s)) return r2; }
+        // clusters are sorted by size: the large ones of the group first, a workgroup of 16 wavefronts each
+        int64_t nbig = 0;
+        while (nbig < gn && cl[(size_t)(g0 + nbig)].m > big_m) ++nbig;
+        if (nbig > 0) {
+            hipLaunchKernelGGL(dc_cluster_kernel<16>, dim3((unsigned)nbig), dim3(1024), 0, s, p, d_clx, d_cl + g0, d_members, d_out,
+                               d_qid, d_qfrom, d_qdis, d_status, d_trace);
+            DPR_HIP(hipGetLastError());
+        }
+        if (gn > nbig) {
+            hipLaunchKernelGGL(dc_cluster_kernel<1>, dim3((unsigned)(gn - nbig)), dim3(64), 0, s, p, d_clx, d_cl + g0 + nbig, d_members, d_out,
+                               d_qid, d_qfrom, d_qdis, d_status, d_trace);
+            DPR_HIP(hipGetLastError());
+        }
+        DPR_HIP(hipStreamSynchronize(s));   // host vectors are reused, the group buffers released
+        g0 = g1;
+    }
+    int32_t st = 0;
+    DPR_HIP(hipMemcpy(&st, d_status, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (st != 0) {
+        set_error("divide-and-conquer: no eligible edge with pendant length < 2 in a cluster (distances >= 2?)");
+        return DPR_ERR_NOCAND;
+    }
+    return DPR_OK;
 }
 
 }  // namespace dpr

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/dipper_hip.h"
+#include "hip_scope.hpp"
 
 namespace dpr {
 

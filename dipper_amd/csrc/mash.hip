@@ -672,8 +672,8 @@ static int mash_encode(MashBuffers& m, hipStream_t s)
     DPR_HIP(hipMalloc(&m.tokens, sizeof(uint4) * (size_t)(m.n * S)));
     DPR_HIP(hipMalloc(&m.tok_cnt, sizeof(int32_t) * (size_t)m.n));
     DPR_HIP(hipMalloc(&m.ref, sizeof(uint64_t) * (size_t)(S + 1)));
-    int* d_nr = nullptr;
-    DPR_HIP(hipMalloc(&d_nr, sizeof(int)));
+    DevBuf<int> d_nr;
+    DPR_HIP(d_nr.alloc(1));
     // The reference list: any sketch gives exact results, one in the middle of the data gives short encodings.  A few
     // candidates (evenly spaced tips) are tried on a sample of the sketches; the one with the fewest tokens is kept.
     int64_t best_tip = 0;
@@ -701,7 +701,7 @@ static int mash_encode(MashBuffers& m, hipStream_t s)
     int nR = 0;
     DPR_HIP(hipMemcpyAsync(&nR, d_nr, sizeof(int), hipMemcpyDeviceToHost, s));
     DPR_HIP(hipStreamSynchronize(s));
-    (void)hipFree(d_nr);
+    d_nr.reset();
     m.ref_n = nR;
     hipLaunchKernelGGL(mash_encode_kernel, dim3((unsigned)((m.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m.sketches, S, m.n,
                        (int64_t)1, m.ref, nR, m.tokens, m.tok_cnt);

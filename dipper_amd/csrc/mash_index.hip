@@ -207,14 +207,13 @@ int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t 
     if (n <= 0) return DPR_OK;
     const int64_t per = (int64_t)kIThreads * kScanItems;
     const int64_t nb = (n + per - 1) / per;
-    uint32_t* bsum = nullptr;
-    DPR_HIP(hipMalloc(&bsum, sizeof(uint32_t) * (size_t)nb));
+    DevBuf<uint32_t> bsum;
+    DPR_HIP(bsum.alloc((size_t)nb));
     hipLaunchKernelGGL(mi_scan_sums_kernel, dim3((unsigned)nb), dim3(kIThreads), 0, s, in, n, bsum);
     hipLaunchKernelGGL(mi_scan_top_kernel, dim3(1), dim3(kIThreads), 0, s, bsum, nb);
     hipLaunchKernelGGL(mi_scan_apply_kernel, dim3((unsigned)nb), dim3(kIThreads), 0, s, in, n, (const uint32_t*)bsum, out);
     const hipError_t e = hipGetLastError();
-    const hipError_t e2 = hipStreamSynchronize(s);       // (the block sums are released here)
-    (void)hipFree(bsum);
+    const hipError_t e2 = hipStreamSynchronize(s);       // (the block sums are released after it, whatever e says)
     if (e != hipSuccess) return hip_fail(e, "mi_inclusive_scan");
     if (e2 != hipSuccess) return hip_fail(e2, "mi_inclusive_scan");
     return DPR_OK;
@@ -534,94 +533,80 @@ int mash_index_build(MashBuffers& m, hipStream_t s)
     MashIndex& ix = m.index;
     const int64_t seg = (int64_t)kIC * S, chunks = (n + kIC - 1) / kIC;
     const unsigned gt = (unsigned)((total + kIThreads - 1) / kIThreads);
-    uint64_t* ks = nullptr;
-    uint32_t *pay = nullptr, *flag = nullptr, *g = nullptr;
-    auto cleanup = [&]() {
-        void* ptrs[] = { ks, pay, flag, g };
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    };
-    auto fail = [&](int rc) { cleanup(); mash_index_free(ix); return rc; };
-#define MI_HIP(x)                                                       \
-    do {                                                                \
-        hipError_t e_ = (x);                                            \
-        if (e_ != hipSuccess) return fail(hip_fail(e_, #x));            \
-    } while (0)
-    MI_HIP(hipMalloc(&ix.mult, sizeof(uint16_t) * (size_t)total));
-    MI_HIP(hipMalloc(&ix.post, sizeof(uint32_t) * (size_t)total));
-    MI_HIP(hipMalloc(&pay, sizeof(uint32_t) * (size_t)total));
-    MI_HIP(hipMalloc(&ks, sizeof(uint64_t) * (size_t)total));
+    DevBuf<uint64_t> ks;
+    DevBuf<uint32_t> pay, flag, g;
+    struct Guard {      // a half-built index does not survive a failed build
+        MashIndex& ix;
+        bool done = false;
+        ~Guard() { if (!done) mash_index_free(ix); }
+    } guard{ ix };
+    DPR_HIP(hipMalloc(&ix.mult, sizeof(uint16_t) * (size_t)total));
+    DPR_HIP(hipMalloc(&ix.post, sizeof(uint32_t) * (size_t)total));
+    DPR_HIP(pay.alloc((size_t)total));
+    DPR_HIP(ks.alloc((size_t)total));
     hipLaunchKernelGGL(mi_payload_kernel, dim3(gt), dim3(kIThreads), 0, s, m.sketches, S, total, pay, ix.mult);
-    MI_HIP(hipGetLastError());
+    DPR_HIP(hipGetLastError());
     // sort every chunk's entries by value: nine rounds of pairwise merges of the (already ascending) sketches
     {
-        uint64_t* k2 = nullptr;
-        uint32_t* p2 = nullptr;
-        MI_HIP(hipMalloc(&k2, sizeof(uint64_t) * (size_t)total));
-        const hipError_t e2 = hipMalloc(&p2, sizeof(uint32_t) * (size_t)total);
-        if (e2 != hipSuccess) { (void)hipFree(k2); return fail(hip_fail(e2, "hipMalloc(merge scratch)")); }
+        DevBuf<uint64_t> k2;        // merge scratch: released at the end of this block
+        DevBuf<uint32_t> p2;
+        DPR_HIP(k2.alloc((size_t)total));
+        DPR_HIP(p2.alloc((size_t)total));
         const int rcs = mi_sort_chunks((const uint64_t*)m.sketches, pay, ks, ix.post, k2, p2, total, seg, S, s);
         const hipError_t es = hipStreamSynchronize(s);
-        (void)hipFree(k2); (void)hipFree(p2);
-        if (rcs != DPR_OK) return fail(rcs);
-        if (es != hipSuccess) return fail(hip_fail(es, "mash_index_build: chunk sort"));
+        if (rcs != DPR_OK) return rcs;
+        if (es != hipSuccess) return hip_fail(es, "mash_index_build: chunk sort");
     }
-    (void)hipFree(pay); pay = nullptr;
+    pay.reset();
     // distinct values of every chunk and the start of their posting lists
-    MI_HIP(hipMalloc(&flag, sizeof(uint32_t) * (size_t)total));
-    MI_HIP(hipMalloc(&g, sizeof(uint32_t) * (size_t)total));
+    DPR_HIP(flag.alloc((size_t)total));
+    DPR_HIP(g.alloc((size_t)total));
     hipLaunchKernelGGL(mi_heads_kernel, dim3(gt), dim3(kIThreads), 0, s, ks, total, seg, flag);
-    MI_HIP(hipGetLastError());
-    if (int rcq = mi_inclusive_scan((const uint32_t*)flag, g, total, s)) return fail(rcq);
+    DPR_HIP(hipGetLastError());
+    if (int rcq = mi_inclusive_scan(flag, g, total, s)) return rcq;
     uint32_t nu = 0;
-    MI_HIP(hipMemcpyAsync(&nu, g + (total - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    MI_HIP(hipStreamSynchronize(s));
+    DPR_HIP(hipMemcpyAsync(&nu, g + (total - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    DPR_HIP(hipStreamSynchronize(s));
     ix.nu = nu;
-    MI_HIP(hipMalloc(&ix.uniq, sizeof(uint64_t) * (size_t)nu));
-    MI_HIP(hipMalloc(&ix.off, sizeof(uint32_t) * ((size_t)nu + 1)));
+    DPR_HIP(hipMalloc(&ix.uniq, sizeof(uint64_t) * (size_t)nu));
+    DPR_HIP(hipMalloc(&ix.off, sizeof(uint32_t) * ((size_t)nu + 1)));
     hipLaunchKernelGGL(mi_compact_kernel, dim3(gt), dim3(kIThreads), 0, s, ks, flag, g, total, ix.uniq, ix.off);
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipMalloc(&ix.ubase, sizeof(uint32_t) * (size_t)(chunks + 1)));
-    MI_HIP(hipMalloc(&ix.shift, sizeof(int32_t) * (size_t)chunks));
-    MI_HIP(hipMalloc(&ix.vmax, sizeof(uint64_t) * (size_t)chunks));
+    DPR_HIP(hipGetLastError());
+    DPR_HIP(hipMalloc(&ix.ubase, sizeof(uint32_t) * (size_t)(chunks + 1)));
+    DPR_HIP(hipMalloc(&ix.shift, sizeof(int32_t) * (size_t)chunks));
+    DPR_HIP(hipMalloc(&ix.vmax, sizeof(uint64_t) * (size_t)chunks));
     hipLaunchKernelGGL(mi_chunks_kernel, dim3((unsigned)((chunks + 1 + kIThreads - 1) / kIThreads)), dim3(kIThreads), 0, s, ks, g, total, seg,
                        chunks, ix.ubase, ix.shift, ix.vmax);
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipMalloc(&ix.bkt, sizeof(uint32_t) * (size_t)(chunks * (kINB + 1))));
+    DPR_HIP(hipGetLastError());
+    DPR_HIP(hipMalloc(&ix.bkt, sizeof(uint32_t) * (size_t)(chunks * (kINB + 1))));
     hipLaunchKernelGGL(mi_buckets_kernel, dim3((unsigned)((nu + kIThreads - 1) / kIThreads)), dim3(kIThreads), 0, s, ix.uniq, ix.off, ix.ubase,
                        ix.shift, (int64_t)nu, seg, ix.bkt);
-    MI_HIP(hipGetLastError());
+    DPR_HIP(hipGetLastError());
     // dense blocks (flag and scan reuse the head-flag buffers: nu <= total)
     {
         const unsigned gu = (unsigned)((nu + kIThreads - 1) / kIThreads);
         hipLaunchKernelGGL(mi_dense_flag_kernel, dim3(gu), dim3(kIThreads), 0, s, ix.off, (int64_t)nu, flag);
-        MI_HIP(hipGetLastError());
-        uint32_t* dscan = nullptr;
-        MI_HIP(hipMalloc(&dscan, sizeof(uint32_t) * (size_t)nu));
-        hipError_t e1 = hipSuccess;
-        if (int rcq = mi_inclusive_scan((const uint32_t*)flag, dscan, (int64_t)nu, s)) { (void)hipFree(dscan); return fail(rcq); }
+        DPR_HIP(hipGetLastError());
+        DevBuf<uint32_t> dscan;     // released at the end of this block
+        DPR_HIP(dscan.alloc((size_t)nu));
+        if (int rcq = mi_inclusive_scan(flag, dscan, (int64_t)nu, s)) return rcq;
         uint32_t nd = 0;
-        if (e1 == hipSuccess) e1 = hipMemcpyAsync(&nd, dscan + (nu - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
-        if (e1 == hipSuccess) e1 = hipMalloc(&ix.dblk, sizeof(int32_t) * (size_t)nu);
-        if (e1 == hipSuccess) e1 = hipMalloc(&ix.dense, sizeof(uint16_t) * ((size_t)nd * kIC + 64));
-        if (e1 == hipSuccess) e1 = hipMemsetAsync(ix.dense, 0x7f, sizeof(uint16_t) * ((size_t)nd * kIC + 64), s);      // absent: position 0x7F7F
-        if (e1 == hipSuccess) {
-            hipLaunchKernelGGL(mi_dense_index_kernel, dim3(gu), dim3(kIThreads), 0, s, flag, dscan, (int64_t)nu, ix.dblk);
-            hipLaunchKernelGGL(mi_dense_fill_kernel, dim3(gt), dim3(kIThreads), 0, s, ix.post, g, ix.dblk, total, ix.dense);
-            e1 = hipGetLastError();
-        }
-        if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
-        (void)hipFree(dscan);
-        if (e1 != hipSuccess) return fail(hip_fail(e1, "mash_index_build: dense blocks"));
+        DPR_HIP(hipMemcpyAsync(&nd, dscan + (nu - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        DPR_HIP(hipStreamSynchronize(s));
+        DPR_HIP(hipMalloc(&ix.dblk, sizeof(int32_t) * (size_t)nu));
+        DPR_HIP(hipMalloc(&ix.dense, sizeof(uint16_t) * ((size_t)nd * kIC + 64)));
+        DPR_HIP(hipMemsetAsync(ix.dense, 0x7f, sizeof(uint16_t) * ((size_t)nd * kIC + 64), s));      // absent: position 0x7F7F
+        hipLaunchKernelGGL(mi_dense_index_kernel, dim3(gu), dim3(kIThreads), 0, s, flag, dscan, (int64_t)nu, ix.dblk);
+        hipLaunchKernelGGL(mi_dense_fill_kernel, dim3(gt), dim3(kIThreads), 0, s, ix.post, g, ix.dblk, total, ix.dense);
+        DPR_HIP(hipGetLastError());
+        DPR_HIP(hipStreamSynchronize(s));
         ix.ndense = nd;
     }
-    MI_HIP(hipMalloc(&ix.dtab, sizeof(double) * (size_t)(S + 1)));
+    DPR_HIP(hipMalloc(&ix.dtab, sizeof(double) * (size_t)(S + 1)));
     hipLaunchKernelGGL(mi_dtab_kernel, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, s, S, m.k, ix.dtab);
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipStreamSynchronize(s));
-#undef MI_HIP
-    cleanup();
+    DPR_HIP(hipGetLastError());
+    DPR_HIP(hipStreamSynchronize(s));
+    guard.done = true;
     ix.chunks = chunks;
     if (log_level("mash") > 0) {
         // (how much of the pair kernel's work takes the dense path: the postings of dense values)

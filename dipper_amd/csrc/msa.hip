@@ -628,8 +628,8 @@ int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hip
     msa_free(m);
     m.n = n; m.L = L; m.W32 = (L + 31) / 32;
     const int64_t W64 = (L + 15) / 16;
-    uint64_t* d_in = nullptr;
-    DPR_HIP(hipMalloc(&d_in, sizeof(uint64_t) * (size_t)(n * W64)));
+    DevBuf<uint64_t> d_in;
+    DPR_HIP(d_in.alloc((size_t)(n * W64)));
     DPR_HIP(hipMemcpyAsync(d_in, packed4, sizeof(uint64_t) * (size_t)(n * W64), hipMemcpyHostToDevice, s));
     DPR_HIP(hipMalloc(&m.planes, sizeof(uint32_t) * (size_t)(4 * n * m.W32)));
     const int64_t total = n * m.W32;
@@ -653,8 +653,7 @@ int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hip
         hipLaunchKernelGGL(msa_xstage_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, n, m.W32, L, m.xstage);
         DPR_HIP(hipGetLastError());
     }
-    DPR_HIP(hipStreamSynchronize(s));
-    DPR_HIP(hipFree(d_in));
+    DPR_HIP(hipStreamSynchronize(s));      // (d_in is read until here)
     return DPR_OK;
 }
 

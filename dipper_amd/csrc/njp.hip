@@ -2015,15 +2015,15 @@ static int njp_run_segment(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t 
     const bool use_graph = q.sh_world <= 1 && todo >= kGraphIters && !timing;      // (DPR_NJ_GRAPH_ITERS above `todo`: eager launches)
     if (use_graph && !q.graph) {
         const auto tg0 = std::chrono::steady_clock::now();
-        hipGraph_t g = nullptr;
+        ScopedGraph g;
         DPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         int rc = DPR_OK;
         for (int k = 0; k < kGraphIters && rc == DPR_OK; ++k) rc = njp_enqueue_iteration(b, s);
-        hipError_t e = hipStreamEndCapture(s, &g);
+        hipError_t e = hipStreamEndCapture(s, g.put());
         if (rc != DPR_OK) return rc;
         if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
         DPR_HIP(hipGraphInstantiate(&q.graph, g, nullptr, nullptr, 0));
-        DPR_HIP(hipGraphDestroy(g));
+        g.reset();
         if (log_level("epoch") > 0)
             std::fprintf(stderr, "[njp] graph capture + instantiate (P=%lld): %.2f ms\n", (long long)q.P,
                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg0).count());

@@ -514,15 +514,15 @@ static int njr_run_segment(std::vector<NjBuffers*>& ranks, int64_t it0, int64_t 
     const int gi = b0.pr.graph_iters;
     const bool use_graph = ranks.size() == 1 && b0.rs.plan == kNjrMailbox && todo >= gi && !timing;
     if (use_graph && !b0.pr.graph) {
-        hipGraph_t g = nullptr;
+        ScopedGraph g;
         DPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         int rc = DPR_OK;
         for (int k = 0; k < gi && rc == DPR_OK; ++k) rc = njr_iteration(ranks, s, false);
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc != DPR_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
+        hipError_t e = hipStreamEndCapture(s, g.put());
+        if (rc != DPR_OK) return rc;
         if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
         e = hipGraphInstantiate(&b0.pr.graph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
+        g.reset();
         if (e != hipSuccess) { b0.pr.graph = nullptr; return hip_fail(e, "hipGraphInstantiate"); }
         b0.rs.launches -= 3 * gi;      // (captured, not launched)
     }

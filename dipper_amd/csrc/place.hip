@@ -1225,23 +1225,21 @@ int place_import_backbone(PlaceBuffers& p, int64_t m, hipStream_t s)
     const bool serial = std::getenv("DPR_IMPORT_SERIAL") != nullptr;
     bool converged = false;
     if (!serial) {
-        int32_t *level = nullptr, *pcnt = nullptr, *pid = nullptr;
-        long long* poff = nullptr;
-        double* pdis = nullptr;
-        int* d_flags = nullptr;
-        unsigned long long* pool_top = nullptr;
+        DevBuf<int32_t> level, pcnt, pid;
+        DevBuf<long long> poff;
+        DevBuf<double> pdis;
+        DevBuf<int> d_flags;
+        DevBuf<unsigned long long> pool_top;
         // (a slot pointing away from the root has nearly all leaves behind it: its passers are the 5-records of their
         // distances in id order, O(5 ln m); measured mean over all slots of a 500 000-tip backbone: see DPR_LOG=import)
         const unsigned long long pool_cap = (unsigned long long)nslots * 192ull;
-        auto release = [&]() { void* q[] = { level, pcnt, poff, pid, pdis, d_flags, pool_top }; for (void* x : q) if (x) (void)hipFree(x); };
-        hipError_t ae = hipMalloc(&level, sizeof(int32_t) * (size_t)nslots);
-        if (ae == hipSuccess) ae = hipMalloc(&pcnt, sizeof(int32_t) * (size_t)nslots);
-        if (ae == hipSuccess) ae = hipMalloc(&poff, sizeof(long long) * (size_t)nslots);
-        if (ae == hipSuccess) ae = hipMalloc(&pid, sizeof(int32_t) * (size_t)pool_cap);
-        if (ae == hipSuccess) ae = hipMalloc(&pdis, sizeof(double) * (size_t)pool_cap);
-        if (ae == hipSuccess) ae = hipMalloc(&d_flags, 2 * sizeof(int));
-        if (ae == hipSuccess) ae = hipMalloc(&pool_top, sizeof(unsigned long long));
-        if (ae != hipSuccess) { release(); return hip_fail(ae, "place_import_backbone: hipMalloc"); }
+        DPR_HIP(level.alloc((size_t)nslots));
+        DPR_HIP(pcnt.alloc((size_t)nslots));
+        DPR_HIP(poff.alloc((size_t)nslots));
+        DPR_HIP(pid.alloc((size_t)pool_cap));
+        DPR_HIP(pdis.alloc((size_t)pool_cap));
+        DPR_HIP(d_flags.alloc(2));
+        DPR_HIP(pool_top.alloc(1));
         DPR_HIP(hipMemsetAsync(level, 0xff, sizeof(int32_t) * (size_t)nslots, s));
         DPR_HIP(hipMemsetAsync(pcnt, 0, sizeof(int32_t) * (size_t)nslots, s));
         DPR_HIP(hipMemsetAsync(pool_top, 0, sizeof(unsigned long long), s));
@@ -1266,10 +1264,9 @@ int place_import_backbone(PlaceBuffers& p, int64_t m, hipStream_t s)
             for (int32_t v : hc) { mx = v > mx ? v : mx; sum += v; }
             std::fprintf(stderr, "[import] %d level rounds, bail %d, passer sequences: longest %d, mean %.1f\n", rounds, (int)bail, mx, sum / (double)nslots);
         }
-        release();
         if (rc) { set_error("place_import_backbone: level rounds failed"); return rc; }
         if (bail) converged = false;
-    }
+    }   // (the level buffers are released here)
     if (!converged) {
         // very deep trees (diameter > 8192 edges), an exhausted passer pool or DPR_IMPORT_SERIAL: the reference's order, leaf by leaf
         hipLaunchKernelGGL(place_init_lists_kernel, dim3((unsigned)((lim + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p, lim);
