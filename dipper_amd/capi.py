@@ -141,6 +141,8 @@ def load_library():
     L.dpr_comm_sum_i32.argtypes = [C.c_void_p, c_i32p, C.c_int64]
     L.dpr_transfer_support.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
     L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
+    L.dpr_transfer_taxa.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
+    L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_ctx_set_tbe_lds.argtypes = [C.c_void_p, C.c_int64]
     L.dpr_comm_sum_i64.argtypes = [C.c_void_p, c_i64p, C.c_int64]
     _LIB = L
@@ -275,6 +277,27 @@ def transfer_support_host(n, main_x, main_y, rep_x, rep_y, phi_sum=None):
     (mx, my, rx, ry), phi_sum = _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum)
     _chk(lib, lib.dpr_transfer_support_host(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), _p(phi_sum, c_i64p)))
     return phi_sum
+
+
+def _taxa_args(n, moved, pairs):
+    if moved is None:
+        moved = np.zeros(max(n, 1), dtype=np.int64)
+    if pairs is None:
+        pairs = np.zeros(1, dtype=np.int64)
+    assert moved.dtype == np.int64 and moved.flags.c_contiguous and len(moved) >= n
+    assert pairs.dtype == np.int64 and pairs.flags.c_contiguous and len(pairs) >= 1
+    return moved, pairs
+
+
+def transfer_taxa_host(n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi_sum=None, moved=None, pairs=None):
+    """(phi_sum, moved, pairs), each added to: phi as transfer_support_host; moved[t] + the counted branches (1000 phi <=
+    cutoff_permille (p - 1)) whose transfer set holds tip t; pairs[0] + the counted branches (host only)"""
+    lib = load_library()
+    (mx, my, rx, ry), phi_sum = _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum)
+    moved, pairs = _taxa_args(n, moved, pairs)
+    _chk(lib, lib.dpr_transfer_taxa_host(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), cutoff_permille,
+                                         _p(phi_sum, c_i64p), _p(moved, c_i64p), _p(pairs, c_i64p)))
+    return phi_sum, moved, pairs
 
 
 def pack4_many(seqs):
@@ -679,6 +702,14 @@ class Dipper:
         _chk(self.L, self.L.dpr_transfer_support(self.h, n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p),
                                                  _p(phi_sum, c_i64p)))
         return phi_sum
+
+    def transfer_taxa(self, n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi_sum=None, moved=None, pairs=None):
+        """transfer_taxa_host's numbers, computed on the device"""
+        (mx, my, rx, ry), phi_sum = _tbe_args(n, main_x, main_y, rep_x, rep_y, phi_sum)
+        moved, pairs = _taxa_args(n, moved, pairs)
+        _chk(self.L, self.L.dpr_transfer_taxa(self.h, n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p),
+                                              cutoff_permille, _p(phi_sum, c_i64p), _p(moved, c_i64p), _p(pairs, c_i64p)))
+        return phi_sum, moved, pairs
 
     def set_tbe_lds(self, nbytes):
         """test hook: LDS budget of transfer_support's tables (0 = its own rule; below one node's table: global memory)"""

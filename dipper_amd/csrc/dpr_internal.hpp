@@ -411,6 +411,7 @@ struct TbeBuffers {
     std::vector<int32_t> hx, hy;         // the uploaded main merge log
     std::vector<int32_t> mpos;           // main-order rank of every leaf
     std::vector<int32_t> node;           // k of every listed main node (internal node n+k with min(|A|, n-|A|) >= 2)
+    std::vector<int32_t> size;           // |A| of every listed main node
     std::vector<int32_t> hphi;           // phi of the listed nodes, copied back
     int2* main_iv = nullptr;             // [listed] main clade as [S, E) in the main tree's DFS leaf order
     int32_t* m = nullptr;                // [n] main-order rank of the leaf at every replicate DFS position
@@ -418,6 +419,12 @@ struct TbeBuffers {
     int32_t* phi = nullptr;              // [listed]
     uint4* scratch = nullptr;            // tables of the global-memory variant (none until a tree needs it)
     size_t scratch_bytes = 0;
+    // dpr_transfer_taxa only (none of it is allocated before its first call)
+    int32_t skip = -1;                   // listed index of the root child left out of the branches (both root children listed), or -1
+    int64_t taxa_cap = 0;                // tips phi_arg and moved hold
+    int32_t* phi_arg = nullptr;          // [2 listed] phi, then the closest replicate node: 2 x its place in rep_iv + (h > n - h)
+    int32_t* moved = nullptr;            // [n] by replicate DFS position: counted branches of this call whose transfer set holds the tip
+    std::vector<int32_t> hmoved;         // moved, copied back
 };
 void tbe_free(TbeBuffers& t);
 

@@ -256,6 +256,10 @@ struct BootstrapOptions {
     int64_t replicates = 0;      // --bootstrap N (0 = off)
     uint64_t seed = 1;           // --bootstrap-seed S
     bool tbe = false;            // --bootstrap-metric tbe: transfer bootstrap expectation instead of Felsenstein's
+    // --bootstrap-taxa FILE: the per-taxon transfer index (either metric)
+    std::ostream* taxa = nullptr;        // rank 0's open FILE (the other ranks: a sink); nullptr = no report
+    int taxaCutoff = 300;                // --bootstrap-taxa-cutoff, per mille (0 .. 999)
+    std::vector<int> slotOfInput;        // tip (slot) of every input record: the report numbers and lists the taxa in input order
 };
 // Support labels of the main tree (merge log mx / my of n tips) from summed counts over `replicates` replicates: the integer
 // percentage, rounded half up, for internal nodes with a non-trivial split, -1 elsewhere.
@@ -267,7 +271,8 @@ std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, c
                                     const std::vector<int64_t>& phi_sum, int64_t replicates);
 // The NJ tree of -i m -o t with --bootstrap: the main tree exactly as findNeighbourJoiningTree builds it, then this rank's
 // replicates (r mod world == rank) on `dev` (one rank) or on a rank-local second context over `packed4` (several ranks), one
-// integer sum of the split counts over the ranks, and the labelled Newick.
+// integer sum of the split counts over the ranks, and the labelled Newick.  With bo.taxa: dpr_transfer_taxa per replicate (next
+// to dpr_split_support, or in place of dpr_transfer_support), one 64-bit sum of moved[] and pairs over the ranks, the report.
 void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& params, const BootstrapOptions& bo,
                                    const uint64_t* packed4, int seqLen, std::vector<std::string>& name, std::ostream& output_);
 

@@ -76,7 +76,14 @@ static const char* kHelp =
     "  --bootstrap-seed arg        Seed of the replicates' column draws (unsigned 64-bit, default 1)\n"
     "  --bootstrap-metric arg      fbp (default): Felsenstein support, the share of replicates that hold\n"
     "                              a split exactly; tbe: transfer bootstrap expectation, one minus the\n"
-    "                              mean share of a split's taxa that must move to reach a replicate\n";
+    "                              mean share of a split's taxa that must move to reach a replicate\n"
+    "  --bootstrap-taxa arg        Write the per-taxon transfer index (rogue taxa) to file arg: for every\n"
+    "                              taxon, in input order, the number and the share of the (branch,\n"
+    "                              replicate) pairs in which it must move to reach the closest replicate\n"
+    "                              branch.  Needs --bootstrap; either metric; the tree file is unchanged\n"
+    "  --bootstrap-taxa-cutoff arg Count a (branch, replicate) pair when its transfer distance is at most\n"
+    "                              arg x (p - 1): a decimal 0 <= arg < 1 with at most three places\n"
+    "                              (default 0.3).  Needs --bootstrap-taxa\n";
 
 struct Opt { const char* lng; char sht; bool has_arg; };
 static const Opt kOpts[] = {
@@ -87,6 +94,7 @@ static const Opt kOpts[] = {
     { "seed", 0, true }, { "device", 0, true }, { "gpus", 0, true }, { "devices", 0, true }, { "transport", 0, true },
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
+    { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -235,6 +243,9 @@ int main(int argc, char** argv)
     BootstrapOptions boot;
     if (vm.count("bootstrap-seed") && !vm.count("bootstrap")) usageError("--bootstrap-seed needs --bootstrap");
     if (vm.count("bootstrap-metric") && !vm.count("bootstrap")) usageError("--bootstrap-metric needs --bootstrap");
+    if (vm.count("bootstrap-taxa") && !vm.count("bootstrap")) usageError("--bootstrap-taxa needs --bootstrap");
+    if (vm.count("bootstrap-taxa-cutoff") && !vm.count("bootstrap-taxa")) usageError("--bootstrap-taxa-cutoff needs --bootstrap-taxa");
+    std::string taxaFile;
     if (vm.count("bootstrap")) {
         auto whole = [](const std::string& v, bool sign_ok) {
             if (v.empty() || v.size() > 20) return false;
@@ -258,6 +269,24 @@ int main(int argc, char** argv)
             const std::string mv = vm["bootstrap-metric"];
             if (mv != "fbp" && mv != "tbe") usageError("--bootstrap-metric: fbp or tbe");
             boot.tbe = mv == "tbe";
+        }
+        if (vm.count("bootstrap-taxa")) {
+            taxaFile = vm["bootstrap-taxa"];
+            if (taxaFile.empty()) usageError("--bootstrap-taxa: a file name");
+            if (taxaFile == vm["output-file"]) usageError("--bootstrap-taxa: the file must differ from the output file (-O)");
+        }
+        if (vm.count("bootstrap-taxa-cutoff")) {
+            // per mille from the text: 0, 0.3, .25, 0.125 -- digits, at most one point, at most three places, an integer part of 0
+            const std::string cv = vm["bootstrap-taxa-cutoff"];
+            const size_t dot = cv.find('.');
+            const std::string ip = cv.substr(0, dot), fp = dot == std::string::npos ? "" : cv.substr(dot + 1);
+            bool ok = !cv.empty() && (!ip.empty() || !fp.empty()) && fp.size() <= 3 && ip.size() <= 20;
+            for (char ch : ip) ok = ok && ch == '0';
+            for (char ch : fp) ok = ok && std::isdigit((unsigned char)ch);
+            if (!ok) usageError("--bootstrap-taxa-cutoff: a decimal 0 <= x < 1 with at most three places (0.3)");
+            int pm = 0;
+            for (size_t i = 0; i < 3; ++i) pm = 10 * pm + (i < fp.size() ? fp[i] - '0' : 0);
+            boot.taxaCutoff = pm;
         }
         const std::string in = strOr(vm, "input-format", "r"), out = strOr(vm, "output-format", "t"), al = strOr(vm, "algorithm", "0");
         if (in != "m") usageError("--bootstrap needs aligned sequences (-i m)");
@@ -526,6 +555,14 @@ int main(int argc, char** argv)
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (multi) { startRanks(ranks, device); adev.reset(new AsyncDeviceContext(rankInfo().device)); }
         auto output_ = open_out();
+        std::unique_ptr<std::ofstream> taxaOut;
+        if (!taxaFile.empty()) {
+            // (opened before the main tree is built: a path that cannot be written ends the run here; rank 0 writes the report)
+            taxaOut = std::make_unique<std::ofstream>(rankInfo().rank == 0 ? taxaFile.c_str() : "/dev/null");
+            if (!*taxaOut) die("ERROR: cannot open the --bootstrap-taxa file: " + taxaFile);
+            boot.taxa = taxaOut.get();
+            boot.slotOfInput = shuffledIds(numSequences, seed);
+        }
         DeviceContext& dev = adev->get();
         MSADeviceArrays msaDeviceArrays;
         MashDeviceArrays mashDeviceArrays;
@@ -600,6 +637,7 @@ int main(int argc, char** argv)
         printRankSummary(dev.ctx);
         // the tree is written: close the output and leave without running the static destructors of the HIP runtime
         output_.reset();
+        taxaOut.reset();
         if (cliLog()) std::cerr << "Main in: " << ms_since(inputStart) << " ms\n";
         std::cerr.flush();
         std::fflush(nullptr);

@@ -7,9 +7,14 @@
 // reaches the replicate loop).  One integer sum over the ranks combines the counts; rank 0 writes the labelled Newick.
 // --bootstrap-metric tbe: dpr_transfer_support (device) in place of dpr_split_support, per-node sums of phi in place of the
 // counts (one 64-bit sum over the ranks), transferLabels in place of supportLabels.
+// --bootstrap-taxa FILE: dpr_transfer_taxa (device) per replicate -- in place of dpr_transfer_support with tbe, next to
+// dpr_split_support with fbp -- adds to moved[tip] and pairs; one more 64-bit sum over the ranks; rank 0 writes FILE.  The report's
+// tips are numbered in input order, so that call gets the trees with the tips renamed from slots to input indices (relabelledLog).
 #include "dipper_host.hpp"
 
+#include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <iostream>
 
 namespace dipper {
@@ -57,6 +62,54 @@ std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, c
     return labels;
 }
 
+// branches of the per-taxon report: internal nodes with p >= 2, the root's two children counting once
+static int64_t taxaBranches(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my)
+{
+    if (n <= 3) return 0;
+    const std::vector<int64_t> size = cladeSizes(n, mx, my);
+    int64_t b = 0;
+    for (int64_t k = 0; k < n - 2; ++k) b += std::min(size[(size_t)(n + k)], n - size[(size_t)(n + k)]) >= 2;
+    // (the root joins two complementary clades: both are branches exactly when both are internal nodes with p >= 2)
+    std::vector<int32_t> real((size_t)n);
+    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
+    for (int64_t it = 0; it < n - 2; ++it) {
+        real[(size_t)mx[(size_t)it]] = (int32_t)(n + it);
+        real[(size_t)my[(size_t)it]] = real[(size_t)(n - it - 1)];
+    }
+    if (real[0] >= n && real[1] >= n && std::min(size[(size_t)real[0]], n - size[(size_t)real[0]]) >= 2) --b;
+    return b;
+}
+
+// The merge log of the same tree with tip `slot` renamed tipOf[slot]: the k-th merge joins the same two nodes into node n+k, so
+// per-node results keep their index; only the slots (the bookkeeping of writeNewickFromMerges, run for the new names) differ.
+static void relabelledLog(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my, const std::vector<int32_t>& tipOf,
+                          std::vector<int32_t>& ox, std::vector<int32_t>& oy)
+{
+    std::vector<int32_t> real((size_t)n), at((size_t)n), slot_of((size_t)std::max<int64_t>(2 * n - 2, n));
+    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = at[(size_t)i] = slot_of[(size_t)i] = (int32_t)i;
+    for (int64_t it = 0; it < n - 2; ++it) {
+        const int32_t x = mx[(size_t)it], y = my[(size_t)it], last = (int32_t)(n - it - 1), v = (int32_t)(n + it);
+        const int32_t a = real[(size_t)x], b = real[(size_t)y];
+        const int32_t sa = slot_of[(size_t)(a < n ? tipOf[(size_t)a] : a)], sb = slot_of[(size_t)(b < n ? tipOf[(size_t)b] : b)];
+        const int32_t lo = std::min(sa, sb), hi = std::max(sa, sb);
+        ox[(size_t)it] = lo; oy[(size_t)it] = hi;
+        at[(size_t)lo] = v; slot_of[(size_t)v] = lo;
+        if (hi != last) { at[(size_t)hi] = at[(size_t)last]; slot_of[(size_t)at[(size_t)hi]] = hi; }
+        real[(size_t)x] = v;
+        real[(size_t)y] = real[(size_t)last];
+    }
+}
+
+// moved / pairs to six decimals, rounded half up, from integers only
+static std::string indexText(int64_t moved, int64_t pairs)
+{
+    if (pairs <= 0) return "0.000000";
+    const unsigned long long q = (unsigned long long)(((unsigned __int128)moved * 1000000u + (unsigned long long)(pairs / 2)) / (unsigned long long)pairs);
+    char buf[48];
+    std::snprintf(buf, sizeof(buf), "%llu.%06llu", q / 1000000ull, q % 1000000ull);
+    return buf;
+}
+
 void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& params, const BootstrapOptions& bo,
                                    const uint64_t* packed4, int seqLen, std::vector<std::string>& name, std::ostream& output_)
 {
@@ -78,7 +131,16 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
 
     const auto tb0 = Clock::now();
     std::vector<int32_t> counts((size_t)k, 0);
-    std::vector<int64_t> phi_sum(bo.tbe ? (size_t)k : 0, 0);
+    std::vector<int64_t> phi_sum(bo.tbe || bo.taxa ? (size_t)k : 0, 0);
+    std::vector<int64_t> moved(bo.taxa ? (size_t)n + 1 : 0, 0);      // by input index; [n]: the counted pairs
+    // the report numbers the tips in input order: its trees go to dpr_transfer_taxa with the tips renamed from slots to that
+    std::vector<int32_t> inputOf, imx, imy, irx, iry;     // (i..: the logs with the tips renamed to input indices)
+    if (bo.taxa) {
+        inputOf.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) inputOf[(size_t)bo.slotOfInput[(size_t)i]] = (int32_t)i;
+        imx.resize((size_t)k); imy.resize((size_t)k); irx.resize((size_t)k); iry.resize((size_t)k);
+        relabelledLog(n, mx, my, inputOf, imx, imy);
+    }
     dpr_ctx* rctx = dev.ctx;
     auto fail = [&](int64_t r, const char* what, int rc) {
         die("ERROR: bootstrap replicate " + std::to_string(r) + ": " + what + " failed (" + std::to_string(rc) + "): " + dpr_last_error());
@@ -104,7 +166,14 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
         const int64_t rdone = dpr_nj_run(rctx, -1, rx.data(), ry.data(), rbx.data(), rby.data(), &rlast);
         if (rdone < 0) fail(r, "dpr_nj_run", (int)rdone);
         const auto t3 = Clock::now();
-        if (bo.tbe) {
+        if (bo.taxa) {
+            relabelledLog(n, rx, ry, inputOf, irx, iry);
+            if (int rc = dpr_transfer_taxa(rctx, n, imx.data(), imy.data(), irx.data(), iry.data(), bo.taxaCutoff, phi_sum.data(),
+                                           moved.data(), moved.data() + n))
+                fail(r, "dpr_transfer_taxa", rc);
+            if (!bo.tbe)
+                if (int rc = dpr_split_support(n, mx.data(), my.data(), rx.data(), ry.data(), counts.data())) fail(r, "dpr_split_support", rc);
+        } else if (bo.tbe) {
             if (int rc = dpr_transfer_support(rctx, n, mx.data(), my.data(), rx.data(), ry.data(), phi_sum.data()))
                 fail(r, "dpr_transfer_support", rc);
         } else if (int rc = dpr_split_support(n, mx.data(), my.data(), rx.data(), ry.data(), counts.data())) {
@@ -118,13 +187,14 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
             dpr_get_timing(rctx, &dist_ms, &nj_ms);
             std::cerr << "  replicate " << r << ": resample " << ms(t0, t1) << " ms, distances " << ms(t1, t2) << " ms (device "
                       << dist_ms << "), NJ " << ms(t2, t3) << " ms (device " << nj_ms << "), "
-                      << (bo.tbe ? "transfer support " : "split count ") << ms(t3, t4) << " ms\n";
+                      << (bo.tbe ? "transfer support " : "split count ") << (bo.taxa ? "and taxa " : "") << ms(t3, t4) << " ms\n";
         }
     }
     if (rctx != dev.ctx) dpr_destroy(rctx);
     else gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, -1), "dpr_msa_resample");
     if (n > 2 && bo.tbe) gpuCheck(dpr_comm_sum_i64(dev.ctx, phi_sum.data(), n - 2), "dpr_comm_sum_i64");
     else if (n > 2) gpuCheck(dpr_comm_sum_i32(dev.ctx, counts.data(), n - 2), "dpr_comm_sum_i32");
+    if (bo.taxa) gpuCheck(dpr_comm_sum_i64(dev.ctx, moved.data(), n + 1), "dpr_comm_sum_i64");
     const auto tb1 = Clock::now();
 
     const std::vector<int32_t> labels = bo.tbe ? transferLabels(n, mx, my, phi_sum, bo.replicates)
@@ -133,6 +203,29 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
     std::cerr << "Bootstrap: " << bo.replicates << " replicates (seed " << bo.seed << ") in " << (long long)ms(tb0, tb1) << " ms, "
               << (mine ? mine_ms / (double)mine : 0.0) << " ms per replicate, " << ri.world << " ranks"
               << (bo.tbe ? ", metric tbe (transfer bootstrap expectation)" : "") << "\n";
+    if (bo.taxa) {
+        const int64_t branches = taxaBranches(n, mx, my), pairs = moved[(size_t)n];
+        char cut[16];
+        std::snprintf(cut, sizeof(cut), "0.%03d", bo.taxaCutoff);
+        std::ostream& os = *bo.taxa;
+        os << "# dipper transfer index: replicates=" << bo.replicates << " seed=" << bo.seed << " cutoff=" << cut << " branches=" << branches
+           << " pairs=" << pairs << "\ntaxon\tmoved\tindex\n";
+        for (int64_t i = 0; i < n; ++i)
+            os << name[(size_t)bo.slotOfInput[(size_t)i]] << "\t" << moved[(size_t)i] << "\t" << indexText(moved[(size_t)i], pairs) << "\n";
+        os.flush();
+        // the five taxa with the largest moved (ties: the earlier one in the input)
+        std::vector<int64_t> top((size_t)n);
+        for (int64_t t = 0; t < n; ++t) top[(size_t)t] = t;
+        const size_t shown = (size_t)std::min<int64_t>(5, n);
+        std::partial_sort(top.begin(), top.begin() + (std::ptrdiff_t)shown, top.end(), [&](int64_t a, int64_t b) {
+            return moved[(size_t)a] != moved[(size_t)b] ? moved[(size_t)a] > moved[(size_t)b] : a < b;
+        });
+        std::cerr << "Transfer index: " << pairs << " of " << branches * bo.replicates << " (branch, replicate) pairs within cutoff " << cut
+                  << "; most moved:";
+        for (size_t i = 0; i < shown; ++i)
+            std::cerr << " " << name[(size_t)bo.slotOfInput[(size_t)top[i]]] << " (" << moved[(size_t)top[i]] << ")";
+        std::cerr << "\n";
+    }
 }
 
 }  // namespace dipper

@@ -416,6 +416,20 @@ int dpr_transfer_support(dpr_ctx *ctx, int64_t n, const int32_t *main_x, const i
  * order; host threads) -- the test reference */
 int dpr_transfer_support_host(int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x, const int32_t *rep_y,
                               int64_t *phi_sum);
+/* Per-taxon transfer index (Lemoine et al. 2018, booster --moved-taxa; no reference counterpart).  The branches are the main
+ * nodes with p >= 2, the root's two children naming one branch (both with p >= 2: the larger node number is left out).  A
+ * (branch, replicate) pair is counted iff 1000 phi <= cutoff_permille (p - 1), 0 <= cutoff_permille <= 999.  Its closest
+ * replicate branch is the internal node v with delta(A, v) = phi whose bipartition has the smallest key (smallest tip index of
+ * the side s without tip 0, then |s|); its transfer set is T = A ^ L_v if h <= n - h, else A ^ (all tips - L_v); |T| = phi.
+ * phi_sum[k] += phi as dpr_transfer_support; moved[t] += [t in T] over this replicate's counted branches (t = tip index,
+ * n entries); *pairs += counted branches.  Bad logs and arguments as dpr_transfer_support; a cutoff outside 0..999 is
+ * DPR_ERR_ARG; n <= 3 is a no-op.  The transfer index of tip t is moved[t] / pairs. */
+int dpr_transfer_taxa(dpr_ctx *ctx, int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x,
+                      const int32_t *rep_y, int cutoff_permille, int64_t *phi_sum, int64_t *moved, int64_t *pairs);
+/* host only, no GPU: the same numbers restated without intervals (clade marks and a walk over the closest node's subtree;
+ * host threads) -- the test reference */
+int dpr_transfer_taxa_host(int64_t n, const int32_t *main_x, const int32_t *main_y, const int32_t *rep_x, const int32_t *rep_y,
+                           int cutoff_permille, int64_t *phi_sum, int64_t *moved, int64_t *pairs);
 /* test hook: LDS bytes dpr_transfer_support may give one workgroup's tables (16 (n/64 + 1) bytes per main node, up to 8 nodes
  * per workgroup; 0 = its own rule: 64 KiB, or one node up to 159 KiB).  A budget below one node's table puts the tables in
  * global memory. */
