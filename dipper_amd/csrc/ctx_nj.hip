@@ -240,7 +240,7 @@ int dpr_reserve_nj(dpr_ctx* c, int64_t n)
     if (want_pruned(c) && n >= 3) {
         NjPruned& q = c->nj[0].pr;
         if (ctx_vshards(c) > 1) { q.sh_world = ctx_vshards(c); q.sh_rank = 0; q.sh_virtual = true; }
-        if (int rc = njp_reserve(q, n, c->stream)) return rc;
+        if (int rc = njp_arena(q, n, c->stream)) return rc;
     }
     DPR_HIP(hipStreamSynchronize(c->stream));
     return DPR_OK;

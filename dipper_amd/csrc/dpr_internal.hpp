@@ -181,6 +181,16 @@ struct NjKernelTiming {
     double us_sum[kNjKernelsMax] = { 0, 0, 0, 0, 0, 0 };
     int64_t samples = 0;
 };
+// one more event of a sampled iteration, recorded on s (on = false: nothing)
+inline int nj_timing_mark(NjKernelTiming* kt, bool on, hipStream_t s)
+{
+    if (!on) return DPR_OK;
+    hipEvent_t e = nullptr;
+    DPR_HIP(hipEventCreate(&e));
+    kt->ev.push_back(e);
+    DPR_HIP(hipEventRecord(e, s));
+    return DPR_OK;
+}
 
 // ---- one-exchange row-sharded streaming NJ (njs.hip) --------------------------------------------------------------
 constexpr int kNjsMaxWorld = 64;
@@ -344,7 +354,7 @@ void njr_free(NjBuffers& b);
 // njp.hip: exact pruned NJ (world == 1)
 int njp_build(NjBuffers& b, hipStream_t s);   // permute the tip-order matrix by ascending row sum into the pruned path's own buffer
 void njp_free(NjPruned& q);                   // everything, the arena included
-int njp_reserve(NjPruned& q, int64_t N, hipStream_t s);   // allocate the arena for N tips ahead of njp_build
+int njp_arena(NjPruned& q, int64_t N, hipStream_t s);     // allocate the arena for N tips (njp_build; ahead of it: dpr_reserve_nj)
 void njp_reset(NjPruned& q);                  // epoch state only (graph, pointers); the arena stays for the next build
 int njp_unit_owner(int64_t strip, int64_t group, int64_t P, int world);
 int njp_run(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t s);   // enqueue `todo` iterations (hipGraph replays)

@@ -35,8 +35,10 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <numeric>
 #include <string>
+#include <type_traits>
 
 namespace dpr {
 
@@ -1402,71 +1404,155 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
 // host side
 // ------------------------------------------------------------------------------------------------
 static int64_t round_up16(int64_t v) { return (v + 15) / 16 * 16; }
-static bool njp_use_post2(const NjPruned& q);
 // (the scan grid, the graph length and the debug buffer are per-context state of NjPruned: two contexts of one process
 // may run different plans, from different host threads)
 // the stamps of the last context that ran with DPR_NJ_PHASES (debug hook njp_phase_stamps; a process-wide pointer to a
 // per-context buffer that stays allocated until the process ends)
 static unsigned long long* g_njp_dbg_last = nullptr;
 
+// ---- launch layer ------------------------------------------------------------------------------------------------
+// One launcher per kernel of the loop, each for finished arguments: njp_args below (single GPU, unit-sharded) or njr.hip's
+// (row-sharded: rs_world > 0 selects the kernels' kRS instantiations).
+// The code object holds the instantiations in the order of their first use; this list keeps that order apart from the order
+// of the launchers, so that the ISA of a change to the host code can be compared with its parent's line by line.  It has no
+// other role: delete it when no such comparison is wanted (the kernels then follow the launchers' order, nothing else changes).
+[[maybe_unused]] static const void* const kNjpInstantiations[] = {
+    (const void*)njp_scan_kernel<false>, (const void*)njp_post2_kernel<kBigNS>, (const void*)njp_post_kernel<64, 1, false>, (const void*)njp_post_kernel<256, kBigNS, false>,
+    (const void*)njp_scan_kernel<true>, (const void*)njp_post_kernel<64, 1, true>, (const void*)njp_finish_kernel<true>, (const void*)njp_finish_kernel<false> };
+
+// the first scan of an epoch: every unit of the rank's test blocks
+int njp_launch_list_all(const NjpArgs& a, hipStream_t s)
+{
+    if (a.ntest > 0) hipLaunchKernelGGL(njp_list_all_kernel, dim3((unsigned)a.ntest), dim3(kThreads), 0, s, a);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+// SCAN: the rank's unit-scan blocks and, with a.do_rows, the new-row blocks behind them
+int njp_launch_scan(const NjpArgs& a, hipStream_t s)
+{
+    const int nrl = a.do_rows ? a.nrb : 0;
+    auto* kernel = a.rs_world > 0 ? njp_scan_kernel<true> : njp_scan_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(a.ugrid + nrl)), dim3(kThreads), 0, s, a.st, (const int32_t*)a.list, (const unsigned long long*)a.cnt,
+                       (const double*)a.xpart, nrl, a);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+// POST: the rank's test blocks and, with a.do_update, the update blocks behind them (N: tips of the run).
+// post2: the large shape on a single rank -- light blocks, maxima of the previous launch (njp_post2_kernel; njp_use_post2 decides)
+int njp_launch_post(const NjpArgs& a0, int64_t N, bool post2, hipStream_t s)
+{
+    NjpArgs a = a0;
+    unsigned ublocks = a.do_update ? (unsigned)((N + kThreads - 1) / kThreads) : 0u;
+    if (post2 && a.do_update) {
+        const unsigned u2 = (unsigned)((N + 2 * kThreads - 1) / (2 * kThreads));      // UM blocks: 512 reference slots and 512 positions each
+        ublocks = u2 > (unsigned)a.nrb ? u2 : (unsigned)a.nrb;
+    }
+    a.nupd = (int)ublocks;
+    if ((unsigned)a.ntest + ublocks == 0u) return DPR_OK;      // (a rank without test blocks in a tests-only launch)
+    auto* kernel = a.rs_world > 0 ? njp_post_kernel<64, 1, true> : post2 ? njp_post2_kernel<kBigNS>
+                 : a.tg == 64 ? njp_post_kernel<64, 1, false> : njp_post_kernel<256, kBigNS, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.ntest + ublocks), dim3(kThreads), 0, s, a.st, (const NjRecord*)a.partials, (const unsigned long long*)a.cnt,
+                       a.blk_cb, a.blk_g0, (const int32_t*)a.pos_of_slot, a.ntest, a.nupd, a);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+// after the last iteration of a segment: the node in quarantine is materialised (row sum, matrix row)
+int njp_launch_finish(const NjpArgs& a, hipStream_t s)
+{
+    auto* kernel = a.rs_world > 0 ? njp_finish_kernel<true> : njp_finish_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.nrb), dim3(kThreads), 0, s, a);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+static bool njp_use_post2(const NjPruned& q)
+{
+    const int ns = njp_ns(q.P);
+    return njp_post2_on() && ns == kBigNS && (q.dbg == nullptr || q.dbg_it >= 0);
+}
+
 // ---- arena -------------------------------------------------------------------------------------------------------
 // Everything the pruned path needs is allocated once per (tips, local ranks) and kept until nj_free: hipMalloc /
 // hipFree of the 7.2 GB matrices (and of ~15 vectors per epoch, 8 epochs per run) serialise with the device and
 // cost more than the distance kernel when a context builds its matrix again (bench.py's steps).
-struct SlabPlan {
-    size_t U, R, Ur, KA, KB, slot_of_pos, pos_of_slot, perm, umin, list, blk_cb, blk_g0, cnt_all, t2_hdr, t2_rmax, t2_cmax, t2_colmin, t2_rowmin, t2_cmin, total;
-    int64_t list_stride;
-};
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-static int64_t prep_blocks(int64_t P, std::vector<int32_t>* hcb, std::vector<int32_t>* hg0)
+// Test blocks of an epoch of P positions, in launch order: (first strip, first row group) each.
+// Single GPU and unit-sharded (rs_world <= 1): njp_ns(P) strips x njp_tg(P) row groups per block (groups >= 32 * strip see the
+// strip); block t belongs to rank t mod world there (njp_unit_owner is the closed form).  Never empty.
+// Row-sharded (njr.hip): the blocks of rank rs_rank -- one strip x 64 row groups ALIGNED to the ownership chunks (a strip's first
+// block may start up to 32 groups in front of the strip's first valid group: those lanes are masked by g >= 32 cb in the
+// kernels).  A rank without units gets 0 (nothing is launched for it); the vectors then hold one placeholder for the upload.
+static int prep_blocks(int64_t P, int rs_world, int rs_rank, std::vector<int32_t>& hcb, std::vector<int32_t>& hg0)
 {
     const int64_t G16 = (P + kUR - 1) / kUR;
-    int64_t cnt = 0;
-    if (njp_ns(P) == 1) {
+    auto add = [&](int64_t c, int64_t g0) { hcb.push_back((int32_t)c); hg0.push_back((int32_t)g0); };
+    if (rs_world > 1) {
+        const int64_t gpc = kNjrChunk / kUR;      // row groups per ownership chunk (64)
         for (int64_t c = 0; 32 * c < G16 && c * kTileCols < P - 1; ++c)
-            for (int64_t g0 = 32 * c; g0 < G16; g0 += njp_tg(P)) {
-                if (hcb) { hcb->push_back((int32_t)c); hg0->push_back((int32_t)g0); }
-                ++cnt;
-            }
+            for (int64_t g0 = (32 * c) / gpc * gpc; g0 < G16; g0 += gpc)
+                if (njr_owner(g0 * kUR, rs_world) == rs_rank) add(c, g0);
+    } else if (njp_ns(P) == 1) {
+        for (int64_t c = 0; 32 * c < G16 && c * kTileCols < P - 1; ++c)
+            for (int64_t g0 = 32 * c; g0 < G16; g0 += njp_tg(P)) add(c, g0);
     } else {
         for (int64_t g0 = 0; g0 < G16; g0 += njp_tg(P))
-            for (int64_t c0 = 0; c0 < njp_strips_of_rows(g0, njp_tg(P), P); c0 += njp_ns(P)) {
-                if (hcb) { hcb->push_back((int32_t)c0); hg0->push_back((int32_t)g0); }
-                ++cnt;
-            }
+            for (int64_t c0 = 0; c0 < njp_strips_of_rows(g0, njp_tg(P), P); c0 += njp_ns(P)) add(c0, g0);
     }
-    if (cnt == 0) { if (hcb) { hcb->push_back(0); hg0->push_back(0); } cnt = 1; }
-    return cnt;
+    const int blocks = (int)hcb.size();
+    if (blocks == 0) add(0, 0);
+    return rs_world > 1 ? blocks : (int)hcb.size();
 }
 static int64_t vec_len(int64_t N) { return (N + kTileCols + 16 + 31) / 32 * 32; }    // 256-byte multiple per vector
-static SlabPlan slab_plan(int64_t P, int64_t N, int local_ranks)
+
+// The per-epoch slab.  Every array is named ONCE here: its length, its pointer in NjPruned and the bytes it starts from
+// (fill < 0: none here -- written before it is read, or initialised by njp_alloc_epoch from q.nprep / host data).
+// P positions of the epoch, N tips of the run (the vectors by position and by slot share one length).
+// slab == nullptr: a dry run that touches nothing (qp may be null); *total receives the bytes in both cases.
+static int njp_carve(NjPruned* qp, char* slab, int64_t P, int64_t N, int local_ranks, hipStream_t s, size_t* total)
 {
-    SlabPlan p;
+    NjPruned dry;
+    NjPruned& q = slab ? *qp : dry;
     const size_t vec = (size_t)vec_len(N);
     const int64_t G16 = (P + kUR - 1) / kUR, S = (P + kTileCols - 1) / kTileCols + 1;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    p.U = take(2 * vec * 8); p.R = take(2 * vec * 8);
-    p.Ur = take(vec * 8); p.KA = take(vec * 8); p.KB = take(vec * 8);
-    p.slot_of_pos = take(vec * 4); p.pos_of_slot = take(vec * 4); p.perm = take(vec * 4);
-    p.umin = take((size_t)(S * G16 * 4) * 8);
-    p.list_stride = unit_total(P) + kScanBlocks + 64;
-    p.list = take((size_t)(p.list_stride * local_ranks) * 4);
+    hipError_t err = hipSuccess;
+    auto take = [&](auto*& ptr, size_t count, int fill = -1) {
+        using T = std::remove_reference_t<decltype(*ptr)>;
+        if (slab) {
+            ptr = reinterpret_cast<T*>(slab + off);
+            if (fill >= 0 && err == hipSuccess) err = hipMemsetAsync(ptr, fill, count * sizeof(T), s);
+        }
+        off += align256(count * sizeof(T));
+    };
+    q.vstride = (int64_t)vec;
+    take(q.U, 2 * vec, 0xff);      // NaN = dead / padding, in both buffers
+    take(q.R, 2 * vec, 0);
+    take(q.Ur, vec, 0xff);         // NaN beyond P
+    take(q.KA, vec, 0);
+    take(q.KB, vec, 0);
+    take(q.slot_of_pos, vec, 0xff);      // -1: dead / padding
+    take(q.pos_of_slot, vec, 0xff);      // -1: slot not alive
+    take(q.perm, vec);
+    q.nunits_alloc = S * G16 * 4;        // four sub-strip bounds per unit
+    take(q.umin, (size_t)q.nunits_alloc);
+    // unit-sharded mode: one list and one counter quadruple per rank held here (all of them for virtual ranks)
+    q.list_stride = unit_total(P) + kScanBlocks + 64;
+    take(q.list, (size_t)(q.list_stride * local_ranks), 0);
     // (capacity for the finest test-block size: a later, smaller epoch of the same arena may use it)
     size_t nprep = 1;
-    {
-        const int64_t G16c = (P + kUR - 1) / kUR;
-        for (int64_t c = 0; 32 * c < G16c && c * kTileCols < P - 1; ++c) nprep += (size_t)((G16c - 32 * c + 31) / 32);
-    }
-    p.blk_cb = take(nprep * 4); p.blk_g0 = take(nprep * 4);
-    p.cnt_all = take((size_t)(4 * local_ranks) * 8);
+    for (int64_t c = 0; 32 * c < G16 && c * kTileCols < P - 1; ++c) nprep += (size_t)((G16 - 32 * c + 31) / 32);
+    take(q.blk_cb, nprep);
+    take(q.blk_g0, nprep);
+    take(q.cnt_all, (size_t)(4 * local_ranks), 0);
     // njp_post2_kernel: header, per-group and per-sub-strip values (M block m writes groups 32 m .. 32 m + 31, sub-strips 4 m .. 4 m + 3)
-    p.t2_hdr = take(256);
-    p.t2_rmax = take((size_t)(2 * 32 * (S + 1)) * 8); p.t2_rowmin = take((size_t)(2 * 32 * (S + 1)) * 8);       // [2]: by iteration parity
-    p.t2_cmax = take((size_t)(2 * 4 * (S + 1)) * 8); p.t2_colmin = take((size_t)(2 * 4 * (S + 1)) * 8);
-    p.t2_cmin = take(nprep * 8);       // one coarse bound per test block
-    p.total = off;
-    return p;
+    take(q.t2_hdr, 256);
+    take(q.t2_rmax, (size_t)(2 * 32 * (S + 1)));       // [2]: by iteration parity
+    take(q.t2_rowmin, (size_t)(2 * 32 * (S + 1)));
+    take(q.t2_cmax, (size_t)(2 * 4 * (S + 1)));
+    take(q.t2_colmin, (size_t)(2 * 4 * (S + 1)));
+    take(q.t2_cmin, nprep);       // one coarse bound per test block
+    *total = off;
+    return err == hipSuccess ? DPR_OK : hip_fail(err, "hipMemsetAsync (epoch slab)");
 }
 // (the same size as NjBuffers::D for N tips, nj_alloc: the two matrix buffers of a context are interchangeable -- the
 //  hand-over to the streaming loop swaps them when the epoch of the moment lives in NjBuffers::D)
@@ -1476,37 +1562,40 @@ static size_t matrix_bytes(int64_t N)
     return (size_t)(rows_alloc * round_up16(N) + kTileCols + 16) * sizeof(double);
 }
 
-static int njp_arena(NjPruned& q, int64_t N, hipStream_t s)
+static int njp_local_ranks(const NjPruned& q) { return q.sh_world > 1 && q.sh_virtual ? q.sh_world : 1; }
+
+// The two slabs of a context for runs of N tips and, with_matrix (single GPU), the pruned path's own matrix buffer, allocated
+// in front of them: on first use, kept while they fit, otherwise released and allocated again as a whole.
+static int njp_reserve_slabs(NjPruned& q, int64_t N, int local_ranks, bool with_matrix, hipStream_t s)
 {
-    const int local_ranks = q.sh_world > 1 && q.sh_virtual ? q.sh_world : 1;
-    const SlabPlan plan = slab_plan(N, N, local_ranks);
-    if (q.arena_D && q.arena_N == N && q.arena_ranks >= local_ranks && q.arena_slab_bytes >= plan.total) return DPR_OK;
-    void* old[] = { q.arena_D, q.arena_slab[0], q.arena_slab[1] };
+    size_t total = 0;
+    if (int rc = njp_carve(nullptr, nullptr, N, N, local_ranks, nullptr, &total)) return rc;
+    if (q.arena_slab[0] && (q.arena_D || !with_matrix) && q.arena_N == N && q.arena_ranks >= local_ranks && q.arena_slab_bytes >= total) return DPR_OK;
+    void* old[] = { with_matrix ? q.arena_D : nullptr, q.arena_slab[0], q.arena_slab[1] };
     for (void* p : old)
         if (p) (void)hipFree(p);
-    q.arena_D = nullptr; q.arena_slab[0] = q.arena_slab[1] = nullptr;
-    DPR_HIP(hipMalloc(&q.arena_D, matrix_bytes(N)));
-    DPR_HIP(hipMemsetAsync(q.arena_D, 0, matrix_bytes(N), s));
-    for (int k = 0; k < 2; ++k) DPR_HIP(hipMalloc(&q.arena_slab[k], plan.total));
-    q.arena_slab_bytes = plan.total;
-    q.arena_N = N;
-    q.arena_ranks = local_ranks;
+    q.arena_slab[0] = q.arena_slab[1] = nullptr;
+    if (with_matrix) {
+        q.arena_D = nullptr;
+        DPR_HIP(hipMalloc(&q.arena_D, matrix_bytes(N)));
+        DPR_HIP(hipMemsetAsync(q.arena_D, 0, matrix_bytes(N), s));
+    }
+    for (int k = 0; k < 2; ++k) DPR_HIP(hipMalloc(&q.arena_slab[k], total));
+    q.arena_slab_bytes = total; q.arena_N = N; q.arena_ranks = local_ranks;
     return DPR_OK;
 }
 
-int njp_reserve(NjPruned& q, int64_t N, hipStream_t s) { return njp_arena(q, N, s); }
+// the arena of a single-GPU context (njp_build; ahead of it: dpr_reserve_nj)
+int njp_arena(NjPruned& q, int64_t N, hipStream_t s) { return njp_reserve_slabs(q, N, njp_local_ranks(q), true, s); }
 
 // point q at the position-space structures of an epoch with P positions (N = total tips: slot arrays) inside
 // matrix buffer `Dbuf` and slab `slab`, and initialise them (all fills ordered on s)
 // rs_world > 1 (row-sharded mode, njr.hip): Dbuf holds the chunks of rank rs_rank only (the caller has cleared it), and the
-// test blocks are this rank's -- one strip x 64 row groups ALIGNED to the ownership chunks (a strip's first block may start
-// up to 32 groups in front of the strip's first valid group: those lanes are masked by g >= 32 cb in the kernels)
+// test blocks are this rank's
 static int njp_alloc_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, char* slab, hipStream_t s, const void* hdr_from = nullptr,
                            int rs_world = 1, int rs_rank = 0)
 {
     if (P >= (int64_t)kTileCols * 1024) { set_error("pruned NJ: the list encoding holds fewer than 524288 positions"); return DPR_ERR_ARG; }
-    const int local_ranks = q.sh_world > 1 && q.sh_virtual ? q.sh_world : 1;
-    const SlabPlan plan = slab_plan(P, N, local_ranks);
     q.P = P;
     q.ld = round_up16(P);
     q.D = Dbuf;
@@ -1514,25 +1603,11 @@ static int njp_alloc_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, char
     // what the permute kernel does not write: columns [P, ld), the group of rows behind position P, the tail pad
     if (rs_world <= 1)
         if (int rc = nj_fill_pads(q.D, q.ld, P, P, rows_alloc, kTileCols + 16, false, s)) return rc;
-    const size_t vec = (size_t)vec_len(N);
-    q.vstride = (int64_t)vec;
-    q.U = reinterpret_cast<double*>(slab + plan.U);
-    q.R = reinterpret_cast<double*>(slab + plan.R);
-    q.Ur = reinterpret_cast<double*>(slab + plan.Ur);
-    q.KA = reinterpret_cast<uint64_t*>(slab + plan.KA);
-    q.KB = reinterpret_cast<uint64_t*>(slab + plan.KB);
-    q.slot_of_pos = reinterpret_cast<int32_t*>(slab + plan.slot_of_pos);
-    q.pos_of_slot = reinterpret_cast<int32_t*>(slab + plan.pos_of_slot);
-    q.perm = reinterpret_cast<int32_t*>(slab + plan.perm);
-    q.umin = reinterpret_cast<uint64_t*>(slab + plan.umin);
-    q.list = reinterpret_cast<int32_t*>(slab + plan.list);
-    q.blk_cb = reinterpret_cast<int32_t*>(slab + plan.blk_cb);
-    q.blk_g0 = reinterpret_cast<int32_t*>(slab + plan.blk_g0);
-    q.cnt_all = reinterpret_cast<unsigned long long*>(slab + plan.cnt_all);
-    q.t2_hdr = slab + plan.t2_hdr;
-    q.t2_rmax = reinterpret_cast<double*>(slab + plan.t2_rmax); q.t2_rowmin = reinterpret_cast<double*>(slab + plan.t2_rowmin);
-    q.t2_cmax = reinterpret_cast<double*>(slab + plan.t2_cmax); q.t2_colmin = reinterpret_cast<double*>(slab + plan.t2_colmin);
-    q.t2_cmin = reinterpret_cast<double*>(slab + plan.t2_cmin);
+    std::vector<int32_t> hcb, hg0;
+    q.nprep = prep_blocks(P, rs_world, rs_rank, hcb, hg0);
+    q.utot = unit_total(P);
+    size_t total = 0;
+    if (int rc = njp_carve(&q, slab, P, N, njp_local_ranks(q), s, &total)) return rc;
     if (hdr_from != nullptr) {
         DPR_HIP(hipMemcpyAsync(q.t2_hdr, hdr_from, 16, hipMemcpyDeviceToDevice, s));      // the range of the run so far
     } else {
@@ -1540,36 +1615,9 @@ static int njp_alloc_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, char
         DPR_HIP(hipMemcpyAsync(q.t2_hdr, h0, sizeof h0, hipMemcpyHostToDevice, s));
         DPR_HIP(hipStreamSynchronize(s));
     }
-    DPR_HIP(hipMemsetAsync(q.U, 0xff, 2 * vec * sizeof(double), s));   // NaN = dead / padding, in both buffers
-    DPR_HIP(hipMemsetAsync(q.R, 0, 2 * vec * sizeof(double), s));
-    DPR_HIP(hipMemsetAsync(q.Ur, 0xff, vec * sizeof(double), s));   // NaN beyond P
-    DPR_HIP(hipMemsetAsync(q.KA, 0, vec * sizeof(uint64_t), s));
-    DPR_HIP(hipMemsetAsync(q.KB, 0, vec * sizeof(uint64_t), s));
-    DPR_HIP(hipMemsetAsync(q.slot_of_pos, 0xff, sizeof(int32_t) * vec, s));   // -1: dead / padding
-    DPR_HIP(hipMemsetAsync(q.pos_of_slot, 0xff, sizeof(int32_t) * vec, s));   // -1: slot not alive
-    const int64_t G16 = (P + kUR - 1) / kUR, S = (P + kTileCols - 1) / kTileCols + 1;
-    q.nunits_alloc = S * G16 * 4;      // four sub-strip bounds per unit
-    q.utot = unit_total(P);
-    {
-        // test blocks: one strip and up to 256 consecutive row groups each (groups >= 32*cb see the strip)
-        std::vector<int32_t> hcb, hg0;
-        if (rs_world > 1) {
-            const int64_t G16r = (P + kUR - 1) / kUR, gpc = kNjrChunk / kUR;      // row groups per ownership chunk (64)
-            for (int64_t c = 0; 32 * c < G16r && c * kTileCols < P - 1; ++c)
-                for (int64_t g0 = (32 * c) / gpc * gpc; g0 < G16r; g0 += gpc)
-                    if (njr_owner(g0 * kUR, rs_world) == rs_rank) { hcb.push_back((int32_t)c); hg0.push_back((int32_t)g0); }
-            q.nprep = (int)hcb.size();
-            if (hcb.empty()) { hcb.push_back(0); hg0.push_back(0); }      // (a rank without units: nprep = 0, nothing is launched for it)
-        } else
-        q.nprep = (int)prep_blocks(P, &hcb, &hg0);
-        DPR_HIP(hipMemcpyAsync(q.blk_cb, hcb.data(), sizeof(int32_t) * hcb.size(), hipMemcpyHostToDevice, s));
-        DPR_HIP(hipMemcpyAsync(q.blk_g0, hg0.data(), sizeof(int32_t) * hg0.size(), hipMemcpyHostToDevice, s));
-        DPR_HIP(hipStreamSynchronize(s));   // the host vectors go out of scope
-    }
-    // unit-sharded mode: one list and one counter quadruple per rank held here (all of them for virtual ranks)
-    q.list_stride = plan.list_stride;
-    DPR_HIP(hipMemsetAsync(q.list, 0, sizeof(int32_t) * (size_t)(q.list_stride * local_ranks), s));
-    DPR_HIP(hipMemsetAsync(q.cnt_all, 0, sizeof(unsigned long long) * (size_t)(4 * local_ranks), s));
+    DPR_HIP(hipMemcpyAsync(q.blk_cb, hcb.data(), sizeof(int32_t) * hcb.size(), hipMemcpyHostToDevice, s));
+    DPR_HIP(hipMemcpyAsync(q.blk_g0, hg0.data(), sizeof(int32_t) * hg0.size(), hipMemcpyHostToDevice, s));
+    DPR_HIP(hipStreamSynchronize(s));   // the host vectors go out of scope
     hipLaunchKernelGGL(njp_fill_u64_kernel, dim3(256), dim3(256), 0, s, (uint64_t*)q.umin, q.nunits_alloc,
                        enc_f64_host(-__builtin_inf()));
     hipLaunchKernelGGL(njp_fill_u64_kernel, dim3(16), dim3(256), 0, s, (uint64_t*)q.t2_cmin, (int64_t)q.nprep, 0xFFF0000000000000ull);   // -inf (plain doubles)
@@ -1578,63 +1626,124 @@ static int njp_alloc_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, char
     return DPR_OK;
 }
 
-static void sort_by_row_sum(std::vector<int32_t>& perm, const std::vector<double>& hU)
+// epoch e of a row-sharded run on this rank: slabs allocated on first use (the arena of the single-GPU path without its matrix
+// buffer), the epoch's structures inside slab e & 1, matrix rows in Dbuf (one half of NjBuffers::D)
+int njp_rs_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, int epoch_index, int rs_rank, int rs_world, const void* hdr_from, hipStream_t s)
 {
+    if (int rc = njp_reserve_slabs(q, N, 1, false, s)) return rc;
+    if (q.graph) { (void)hipGraphExecDestroy(q.graph); q.graph = nullptr; }
+    q.sh_world = 1; q.sh_rank = 0; q.sh_virtual = false;
+    q.epoch_index = epoch_index;
+    if (int rc = njp_alloc_epoch(q, P, N, Dbuf, q.arena_slab[epoch_index & 1], s, hdr_from, rs_world, rs_rank)) return rc;
+    q.active = true;
+    return DPR_OK;
+}
+
+// ---- the steps every epoch constructor takes (njp_build, njp_rebuild_epoch, njp_from_slots; njr_build, njr_rebuild_epoch) ----
+// Position order of a new epoch: the n live ones of the P source positions (slot_of_pos >= 0; nullptr: all of them, n = P),
+// ascending by their row sums dU[p], NaN last, stable.  (Ur does not tell who lives: the node in quarantine carries NaN there.)
+// stream_idle: the caller has waited for s (between iterations: blocking copies); otherwise the row sums are fetched on s.
+int njp_epoch_order(const double* dU, const int32_t* slot_of_pos, int64_t P, int64_t n, std::vector<int32_t>& perm, bool stream_idle, hipStream_t s)
+{
+    std::vector<double> hU((size_t)P);
+    if (stream_idle) {
+        DPR_HIP(hipMemcpy(hU.data(), dU, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost));
+    } else {
+        DPR_HIP(hipMemcpyAsync(hU.data(), dU, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, s));
+        DPR_HIP(hipStreamSynchronize(s));
+    }
+    perm.clear();
+    perm.reserve((size_t)n);
+    if (slot_of_pos) {
+        std::vector<int32_t> hslot((size_t)P);
+        DPR_HIP(hipMemcpy(hslot.data(), slot_of_pos, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost));
+        for (int64_t p = 0; p < P; ++p)
+            if (hslot[(size_t)p] >= 0) perm.push_back((int32_t)p);
+    } else {
+        perm.resize((size_t)P);
+        std::iota(perm.begin(), perm.end(), 0);
+    }
+    if ((int64_t)perm.size() != n) { set_error("pruned NJ epoch: live positions do not match the active size"); return DPR_ERR_STATE; }
     std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t c) {
         const double ua = hU[(size_t)a], uc = hU[(size_t)c];
         if (ua != ua) return false;      // NaN last
         if (uc != uc) return true;
         return ua < uc;
     });
+    return DPR_OK;
+}
+// vectors of the new epoch q (n positions, q.perm uploaded) from the source's current row sums; slot_src: the source's
+// slot_of_pos, nullptr when the source is in slot order (the tip-order sums, the streaming loop's).  Iteration `it` reads the
+// U buffer written here.
+int njp_init_vectors(NjPruned& q, const double* U_src, const int32_t* slot_src, int64_t n, int64_t it, hipStream_t s)
+{
+    hipLaunchKernelGGL(njp_init_vectors_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                       U_src, (const int32_t*)q.perm, slot_src, n, n, q.U + (it & 1) * q.vstride, q.Ur, q.KA, q.KB, q.slot_of_pos, q.pos_of_slot);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+// iteration state of a fresh epoch: nothing in quarantine (every row sum is in memory), empty lists.  `st` is the host's copy of
+// the state: the caller waits for the stream before it goes out of scope.
+int njp_put_fresh_state(NjState* d_st, NjState& st, hipStream_t s)
+{
+    st.pnew[0] = -1; st.pnew[1] = -1;
+    for (auto& c : st.cnt_list) c = 0ull;
+    DPR_HIP(hipMemcpyAsync(d_st, &st, sizeof(NjState), hipMemcpyHostToDevice, s));
+    return DPR_OK;
+}
+// the large-shape post kernel's bounds need the range of the entries: one pass over the n x n source matrix (once per run, and
+// again after streaming iterations, which create values nobody tracked)
+static int njp_find_range(NjPruned& q, const double* D, int64_t ld, int64_t n, hipStream_t s)
+{
+    q.range_known = njp_use_post2(q);
+    if (!q.range_known) return DPR_OK;
+    hipLaunchKernelGGL(njp_range_kernel, dim3(2048), dim3(kThreads), 0, s, D, ld, n, (unsigned long long*)q.t2_hdr);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+// plan of a context, at build: blocks of the unit scan and iterations per captured graph
+void njp_plan_from_env(NjPruned& q)
+{
+    // blocks of the unit scan (tests shrink it so that every block walks several units and cnt > grid)
+    // default: 256 blocks while an iteration lists ~100 units (a 1000-block grid takes ~1.5 us just to start; NJ 515 ->
+    // 512 ms at 30 000 tips), 512 above (round 2: 1024; every block of the post kernels reduces one record per scan block --
+    // NJ at 100 000 tips 2.10 / 2.07 / 2.06 / 2.08 / 2.10 s with 256 / 384 / 512 / 768 / 1024, round 3)
+    // Round 4: 512 for every size.  The listing rate depends on the data and on the age of the epoch (4 - 60 units per
+    // iteration in a fresh epoch, 150 - 350 in an old one at 30 000 tips, 770 - 1 180 at 100 000; branch lengths x 5 / x 25:
+    // 500 / 820 on average): with 256 blocks the diverged inputs took 574 / 663 ms, with 512 blocks 544 / 614 ms, the bench
+    // input 479.5 vs 481.5 ms.  A grid that followed the watched rate (256 / 512 / 1 024, graph re-captured) was slower than
+    // 512 throughout: 2.08 vs 2.05 s at 100 000 tips, 657 vs 614 ms on the x 25 input (profiles/r4/scan_grid_*.txt).
+    const char* e = std::getenv("DPR_NJP_GRID");
+    const int g = e ? std::atoi(e) : 512;
+    q.scan_grid = g < 1 ? 1 : (g > 1024 ? 1024 : g);
+    if (const char* gi = std::getenv("DPR_NJ_GRAPH_ITERS")) { const int v = std::atoi(gi); if (v >= 1 && v <= 4096) q.graph_iters = v; }
 }
 
 int njp_build(NjBuffers& b, hipStream_t s)
 {
-    {   // blocks of the unit scan (tests shrink it so that every block walks several units and cnt > grid)
-        // default: 256 blocks while an iteration lists ~100 units (a 1000-block grid takes ~1.5 us just to start; NJ 515 ->
-        // 512 ms at 30 000 tips), 512 above (round 2: 1024; every block of the post kernels reduces one record per scan block --
-        // NJ at 100 000 tips 2.10 / 2.07 / 2.06 / 2.08 / 2.10 s with 256 / 384 / 512 / 768 / 1024, round 3)
-        // Round 4: 512 for every size.  The listing rate depends on the data and on the age of the epoch (4 - 60 units per
-        // iteration in a fresh epoch, 150 - 350 in an old one at 30 000 tips, 770 - 1 180 at 100 000; branch lengths x 5 / x 25:
-        // 500 / 820 on average): with 256 blocks the diverged inputs took 574 / 663 ms, with 512 blocks 544 / 614 ms, the bench
-        // input 479.5 vs 481.5 ms.  A grid that followed the watched rate (256 / 512 / 1 024, graph re-captured) was slower than
-        // 512 throughout: 2.08 vs 2.05 s at 100 000 tips, 657 vs 614 ms on the x 25 input (profiles/r4/scan_grid_*.txt).
-        b.pr.scan_grid = njp_scan_grid_default();
-    }
-    if (const char* e = std::getenv("DPR_NJ_ADAPTIVE")) b.pr.adaptive = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("DPR_NJ_STREAM_FRAC")) b.pr.stream_frac = std::atof(e);
-    b.pr.stream_iterations = 0; b.pr.stream_epochs = 0;
-    if (const char* e = std::getenv("DPR_NJ_GRAPH_ITERS")) { const int v = std::atoi(e); if (v >= 1 && v <= 4096) b.pr.graph_iters = v; }
+    NjPruned& q = b.pr;
+    njp_plan_from_env(q);
+    if (const char* e = std::getenv("DPR_NJ_ADAPTIVE")) q.adaptive = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("DPR_NJ_STREAM_FRAC")) q.stream_frac = std::atof(e);
+    q.stream_iterations = 0; q.stream_epochs = 0;
     if (const char* e = std::getenv("DPR_NJ_PHASES")) {
-        b.pr.dbg_it = std::atoll(e);
-        if (!b.pr.dbg) DPR_HIP(hipMalloc(&b.pr.dbg, sizeof(unsigned long long) * 4 * 2048 * 8));
-        DPR_HIP(hipMemsetAsync(b.pr.dbg, 0, sizeof(unsigned long long) * 4 * 2048 * 8, s));
-        g_njp_dbg_last = b.pr.dbg;
+        q.dbg_it = std::atoll(e);
+        if (!q.dbg) DPR_HIP(hipMalloc(&q.dbg, sizeof(unsigned long long) * 4 * 2048 * 8));
+        DPR_HIP(hipMemsetAsync(q.dbg, 0, sizeof(unsigned long long) * 4 * 2048 * 8, s));
+        g_njp_dbg_last = q.dbg;
     }
     // b.D / b.U hold the matrix and the row sums in tip order (world == 1).  Sort by U ascending.
     const int64_t N = b.N;
-    std::vector<double> hU((size_t)N);
-    DPR_HIP(hipMemcpyAsync(hU.data(), b.U, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    DPR_HIP(hipStreamSynchronize(s));
-    std::vector<int32_t> perm((size_t)N);
-    std::iota(perm.begin(), perm.end(), 0);
-    sort_by_row_sum(perm, hU);
-    NjPruned& q = b.pr;
+    std::vector<int32_t> perm;
+    if (int rc = njp_epoch_order(b.U, nullptr, N, N, perm, false, s)) return rc;
     if (int rc = njp_arena(q, N, s)) return rc;
     q.epoch_index = 0;
     if (int rc = njp_alloc_epoch(q, N, N, q.arena_D, q.arena_slab[0], s)) return rc;
     q.utot0 = q.utot;
     DPR_HIP(hipMemcpyAsync(q.perm, perm.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, s));
     njp_launch_permute(b.D, b.ld, q.D, q.ld, q.perm, N, s);
-    q.range_known = false;
-    if (njp_use_post2(q)) {        // the large-shape post kernel's bounds need the range of the entries (one pass, once per run)
-        hipLaunchKernelGGL(njp_range_kernel, dim3(2048), dim3(kThreads), 0, s, (const double*)b.D, b.ld, N, (unsigned long long*)q.t2_hdr);
-        q.range_known = true;
-    }
-    // (iteration 0 reads U buffer 0)
-    hipLaunchKernelGGL(njp_init_vectors_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       b.U, q.perm, (const int32_t*)nullptr, N, N, q.U, q.Ur, q.KA, q.KB, q.slot_of_pos, q.pos_of_slot);
-    DPR_HIP(hipGetLastError());
+    if (int rc = njp_find_range(q, b.D, b.ld, N, s)) return rc;
+    if (int rc = njp_init_vectors(q, b.U, nullptr, N, 0, s)) return rc;      // (iteration 0 reads U buffer 0)
     DPR_HIP(hipStreamSynchronize(s));   // `perm` goes out of scope
     // (the tip-order matrix in b.D is dead from here on: the odd epochs use its storage)
     q.active = true;
@@ -1662,21 +1771,12 @@ static int njp_rebuild_epoch(NjBuffers& b, hipStream_t s, bool* rebuilt)
     };
     NjState st;
     DPR_HIP(hipMemcpy(&st, b.st, sizeof(NjState), hipMemcpyDeviceToHost));
-    const int64_t n = st.n, Pold = q.P;
+    const int64_t n = st.n;
     if (st.status != 0 || n < 3) return DPR_OK;
-    std::vector<double> hU((size_t)Pold);
-    std::vector<int32_t> hslot((size_t)Pold);
-    const double* Ucur = q.U + (st.it & 1) * q.vstride;
-    DPR_HIP(hipMemcpy(hU.data(), Ucur, sizeof(double) * (size_t)Pold, hipMemcpyDeviceToHost));
-    DPR_HIP(hipMemcpy(hslot.data(), q.slot_of_pos, sizeof(int32_t) * (size_t)Pold, hipMemcpyDeviceToHost));
-    lap("state + vectors to the host");
+    const double* Ucur = njp_current_u(q, st.it);
     std::vector<int32_t> perm;
-    perm.reserve((size_t)n);
-    for (int64_t p = 0; p < Pold; ++p)
-        if (hslot[(size_t)p] >= 0) perm.push_back((int32_t)p);      // (Ur does not tell: the node in quarantine carries NaN there)
-    if ((int64_t)perm.size() != n) { set_error("njp_rebuild_epoch: live positions do not match the active size"); return DPR_ERR_STATE; }
-    sort_by_row_sum(perm, hU);
-    lap("sort");
+    if (int rc = njp_epoch_order(Ucur, q.slot_of_pos, q.P, n, perm, true, s)) return rc;
+    lap("state + vectors to the host, sort");
     if (q.graph) { (void)hipGraphExecDestroy(q.graph); q.graph = nullptr; }
     const NjPruned old = q;              // the old epoch's pointers (read by the permute / init kernels below)
     const int e = old.epoch_index + 1;
@@ -1685,14 +1785,8 @@ static int njp_rebuild_epoch(NjBuffers& b, hipStream_t s, bool* rebuilt)
     lap("njp_alloc_epoch");
     DPR_HIP(hipMemcpyAsync(q.perm, perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
     njp_launch_permute(old.D, old.ld, q.D, q.ld, q.perm, n, s);
-    hipLaunchKernelGGL(njp_init_vectors_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       Ucur, q.perm, (const int32_t*)old.slot_of_pos, n, n, q.U + (st.it & 1) * q.vstride, q.Ur, q.KA, q.KB,
-                       q.slot_of_pos, q.pos_of_slot);
-    DPR_HIP(hipGetLastError());
-    // iteration state: nothing in quarantine (every row sum is in memory), empty lists
-    st.pnew[0] = -1; st.pnew[1] = -1;
-    for (auto& c : st.cnt_list) c = 0ull;
-    DPR_HIP(hipMemcpyAsync(b.st, &st, sizeof(NjState), hipMemcpyHostToDevice, s));
+    if (int rc = njp_init_vectors(q, Ucur, old.slot_of_pos, n, st.it, s)) return rc;
+    if (int rc = njp_put_fresh_state(b.st, st, s)) return rc;
     lap("enqueue");
     DPR_HIP(hipStreamSynchronize(s));    // `st`, `perm` are host objects
     lap("device work");
@@ -1739,27 +1833,15 @@ static int njp_from_slots(NjBuffers& b, hipStream_t s)
     DPR_HIP(hipMemcpy(&st, b.st, sizeof(NjState), hipMemcpyDeviceToHost));
     const int64_t n = st.n;
     if (st.status != 0 || n < 3) return DPR_OK;
-    std::vector<double> hU((size_t)n);
-    DPR_HIP(hipMemcpy(hU.data(), b.U, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    std::vector<int32_t> perm((size_t)n);
-    std::iota(perm.begin(), perm.end(), 0);
-    sort_by_row_sum(perm, hU);
+    std::vector<int32_t> perm;
+    if (int rc = njp_epoch_order(b.U, nullptr, n, n, perm, true, s)) return rc;
     q.epoch_index = 0;                       // even: the epoch lives in arena_D (b.D holds the slot-space matrix it is built from)
     if (int rc = njp_alloc_epoch(q, n, b.N, q.arena_D, q.arena_slab[0], s)) return rc;
     DPR_HIP(hipMemcpyAsync(q.perm, perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
     njp_launch_permute((const double*)b.D, b.ld, q.D, q.ld, (const int32_t*)q.perm, n, s);
-    q.range_known = false;
-    if (njp_use_post2(q)) {        // (the streaming iterations created values nobody tracked: reduce the matrix again)
-        hipLaunchKernelGGL(njp_range_kernel, dim3(2048), dim3(kThreads), 0, s, (const double*)b.D, b.ld, n, (unsigned long long*)q.t2_hdr);
-        q.range_known = true;
-    }
-    hipLaunchKernelGGL(njp_init_vectors_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       (const double*)b.U, (const int32_t*)q.perm, (const int32_t*)nullptr, n, n, q.U + (st.it & 1) * q.vstride, q.Ur, q.KA, q.KB,
-                       q.slot_of_pos, q.pos_of_slot);
-    DPR_HIP(hipGetLastError());
-    st.pnew[0] = -1; st.pnew[1] = -1;
-    for (auto& c : st.cnt_list) c = 0ull;
-    DPR_HIP(hipMemcpyAsync(b.st, &st, sizeof(NjState), hipMemcpyHostToDevice, s));
+    if (int rc = njp_find_range(q, b.D, b.ld, n, s)) return rc;
+    if (int rc = njp_init_vectors(q, b.U, nullptr, n, st.it, s)) return rc;
+    if (int rc = njp_put_fresh_state(b.st, st, s)) return rc;
     DPR_HIP(hipStreamSynchronize(s));        // `st`, `perm` are host objects
     q.slots_mode = false;
     return DPR_OK;
@@ -1802,6 +1884,9 @@ void njp_free(NjPruned& q)
 // unit-sharded mode: unit-scan blocks per rank and unit records in total
 static int njp_grid_rank(const NjPruned& q) { return q.sh_world > 1 ? (q.scan_grid / q.sh_world > 0 ? q.scan_grid / q.sh_world : 1) : q.scan_grid; }
 static int njp_grid_total(const NjPruned& q) { return q.sh_world > 1 ? njp_grid_rank(q) * q.sh_world : q.scan_grid; }
+// the ranks this process launches for: [first, last)
+static int njp_first_rank(const NjPruned& q) { return q.sh_world > 1 && !q.sh_virtual ? q.sh_rank : 0; }
+static int njp_last_rank(const NjPruned& q) { return q.sh_world > 1 ? (q.sh_virtual ? q.sh_world : q.sh_rank + 1) : 1; }
 
 // kernel arguments of rank v (its own list and counters; v is ignored outside the unit-sharded mode)
 static NjpArgs njp_args(NjBuffers& b, int v)
@@ -1809,7 +1894,7 @@ static NjpArgs njp_args(NjBuffers& b, int v)
     NjPruned& q = b.pr;
     const bool sh = q.sh_world > 1;
     const int slot = sh && q.sh_virtual ? v : 0;             // local storage index of this rank
-    NjpArgs a;
+    NjpArgs a{};                                             // (rs_world = 0: not row-sharded)
     a.D = q.D; a.ld = q.ld; a.st = b.st;
     a.U = q.U; a.R = q.R; a.vstride = q.vstride;
     a.Ur = q.Ur; a.KA = q.KA; a.KB = q.KB; a.slot_of_pos = q.slot_of_pos; a.pos_of_slot = q.pos_of_slot;
@@ -1835,156 +1920,70 @@ static NjpArgs njp_args(NjBuffers& b, int v)
     return a;
 }
 
-static int njp_launch_scan(NjBuffers& b, hipStream_t s, int v, bool rows)
-{
-    NjpArgs a = njp_args(b, v);
-    a.do_rows = rows ? 1 : 0;
-    hipLaunchKernelGGL((njp_scan_kernel<false>), dim3((unsigned)(a.ugrid + (rows ? a.nrb : 0))), dim3(kThreads), 0, s, a.st, (const int32_t*)a.list,
-                       (const unsigned long long*)a.cnt, (const double*)a.xpart, rows ? a.nrb : 0, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-static bool njp_use_post2(const NjPruned& q)
-{
-    const int ns = njp_ns(q.P);
-    return njp_post2_on() && ns == kBigNS && (q.dbg == nullptr || q.dbg_it >= 0);
-}
-
-static int njp_launch_post(NjBuffers& b, hipStream_t s, int v, bool update)
-{
-    NjpArgs a = njp_args(b, v);
-    a.do_update = update ? 1 : 0;
-    const unsigned ublocks = update ? (unsigned)((b.N + kThreads - 1) / kThreads) : 0u;
-    a.nupd = (int)ublocks;
-    if ((unsigned)a.ntest + ublocks == 0u) return DPR_OK;      // (a rank without test blocks in a tests-only launch)
-    // large shape on a single rank: light blocks, maxima of the previous launch (njp_post2_kernel; DPR_NJP_POST2=0: the fused kernel)
-    if (njp_use_post2(b.pr)) {
-        const unsigned u2 = update ? (unsigned)((b.N + 2 * kThreads - 1) / (2 * kThreads)) : 0u;      // UM blocks: 512 reference slots and 512 positions each
-        const unsigned um = !update ? 0u : (u2 > (unsigned)a.nrb ? u2 : (unsigned)a.nrb);
-        a.nupd = (int)um;
-        if ((unsigned)a.ntest + um == 0u) return DPR_OK;
-        hipLaunchKernelGGL((njp_post2_kernel<kBigNS>), dim3((unsigned)a.ntest + um), dim3(kThreads), 0, s, a.st, (const NjRecord*)a.partials, (const unsigned long long*)a.cnt, a.blk_cb, a.blk_g0, (const int32_t*)a.pos_of_slot, a.ntest, a.nupd, a);
-        DPR_HIP(hipGetLastError());
-        return DPR_OK;
-    }
-    if (a.tg == 64) hipLaunchKernelGGL((njp_post_kernel<64, 1, false>), dim3((unsigned)a.ntest + ublocks), dim3(kThreads), 0, s, a.st, (const NjRecord*)a.partials, (const unsigned long long*)a.cnt, a.blk_cb, a.blk_g0, (const int32_t*)a.pos_of_slot, a.ntest, a.nupd, a);
-    else hipLaunchKernelGGL((njp_post_kernel<256, kBigNS, false>), dim3((unsigned)a.ntest + ublocks), dim3(kThreads), 0, s, a.st, (const NjRecord*)a.partials, (const unsigned long long*)a.cnt, a.blk_cb, a.blk_g0, (const int32_t*)a.pos_of_slot, a.ntest, a.nupd, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-
-// ---- the row-sharded instantiations (njr.hip builds the arguments and owns the loop) ----------------------------------
-int njp_rs_launch_list_all(const NjpArgs& a, hipStream_t s)
-{
-    if (a.ntest > 0) hipLaunchKernelGGL(njp_list_all_kernel, dim3((unsigned)a.ntest), dim3(kThreads), 0, s, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-int njp_rs_launch_scan(const NjpArgs& a, hipStream_t s)
-{
-    hipLaunchKernelGGL((njp_scan_kernel<true>), dim3((unsigned)(a.ugrid + a.nrb)), dim3(kThreads), 0, s, a.st, (const int32_t*)a.list,
-                       (const unsigned long long*)a.cnt, (const double*)a.xpart, a.nrb, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-int njp_rs_launch_post(const NjpArgs& a0, int64_t N, hipStream_t s)
-{
-    NjpArgs a = a0;
-    const unsigned ublocks = (unsigned)((N + kThreads - 1) / kThreads);
-    a.nupd = (int)ublocks;
-    hipLaunchKernelGGL((njp_post_kernel<64, 1, true>), dim3((unsigned)a.ntest + ublocks), dim3(kThreads), 0, s, a.st, (const NjRecord*)a.partials,
-                       (const unsigned long long*)a.cnt, a.blk_cb, a.blk_g0, (const int32_t*)a.pos_of_slot, a.ntest, a.nupd, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-int njp_rs_launch_finish(const NjpArgs& a, hipStream_t s)
-{
-    hipLaunchKernelGGL((njp_finish_kernel<true>), dim3((unsigned)a.nrb), dim3(kThreads), 0, s, a);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-// epoch e of a row-sharded run on this rank: slabs allocated on first use (the arena of the single-GPU path without its matrix
-// buffer), the epoch's structures inside slab e & 1, matrix rows in Dbuf (one half of NjBuffers::D)
-int njp_rs_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, int epoch_index, int rs_rank, int rs_world, const void* hdr_from, hipStream_t s)
-{
-    const SlabPlan plan = slab_plan(N, N, 1);
-    if (!q.arena_slab[0] || q.arena_N != N || q.arena_slab_bytes < plan.total) {
-        for (int k = 0; k < 2; ++k) { if (q.arena_slab[k]) (void)hipFree(q.arena_slab[k]); q.arena_slab[k] = nullptr; }
-        for (int k = 0; k < 2; ++k) DPR_HIP(hipMalloc(&q.arena_slab[k], plan.total));
-        q.arena_slab_bytes = plan.total; q.arena_N = N; q.arena_ranks = 1;
-    }
-    if (q.graph) { (void)hipGraphExecDestroy(q.graph); q.graph = nullptr; }
-    q.sh_world = 1; q.sh_rank = 0; q.sh_virtual = false;
-    q.epoch_index = epoch_index;
-    if (int rc = njp_alloc_epoch(q, P, N, Dbuf, q.arena_slab[epoch_index & 1], s, hdr_from, rs_world, rs_rank)) return rc;
-    q.active = true;
-    return DPR_OK;
-}
-// vectors of a new epoch from the previous one's (or from the tip-order row sums: slot_src = nullptr), as njp_build / njp_rebuild_epoch do
-int njp_rs_init_vectors(NjPruned& q, const double* U_src, const int32_t* slot_src, int64_t P, int64_t n, int64_t it, hipStream_t s)
-{
-    hipLaunchKernelGGL(njp_init_vectors_kernel, dim3((unsigned)((P + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       U_src, (const int32_t*)q.perm, slot_src, P, n, q.U + (it & 1) * q.vstride, q.Ur, q.KA, q.KB, q.slot_of_pos, q.pos_of_slot);
-    DPR_HIP(hipGetLastError());
-    return DPR_OK;
-}
-void njp_rs_sort_by_row_sum(std::vector<int32_t>& perm, const std::vector<double>& hU) { sort_by_row_sum(perm, hU); }
-int64_t njp_vec_len(int64_t N) { return vec_len(N); }
-int njp_scan_grid_default()
-{
-    const char* e = std::getenv("DPR_NJP_GRID");
-    const int g = e ? std::atoi(e) : 512;
-    return g < 1 ? 1 : (g > 1024 ? 1024 : g);
-}
-
 // one iteration: SCAN -> POST; every kernel reads its iteration index from the device state.
 // sample: bracket the launches by HIP events (NjKernelTiming; eager runs only)
 static int njp_enqueue_iteration(NjBuffers& b, hipStream_t s, bool sample = false)
 {
     NjPruned& q = b.pr;
+    const bool post2 = njp_use_post2(q);
     if (q.sh_world <= 1) {
-        auto mark = [&]() -> int {
-            if (!sample) return DPR_OK;
-            hipEvent_t e = nullptr;
-            DPR_HIP(hipEventCreate(&e));
-            b.kt->ev.push_back(e);
-            DPR_HIP(hipEventRecord(e, s));
-            return DPR_OK;
-        };
+        const NjpArgs a = njp_args(b, 0);
         if (sample) { b.kt->nk = 3; njp_set_kernel_names(nullptr); }      // the third interval holds nothing: what an event pair itself costs
-        if (int rc = mark()) return rc;
-        if (int rc = njp_launch_scan(b, s, 0, true)) return rc;
-        if (int rc = mark()) return rc;
-        if (int rc = njp_launch_post(b, s, 0, true)) return rc;
-        if (int rc = mark()) return rc;
-        return mark();
+        if (int rc = nj_timing_mark(b.kt, sample, s)) return rc;
+        if (int rc = njp_launch_scan(a, s)) return rc;
+        if (int rc = nj_timing_mark(b.kt, sample, s)) return rc;
+        if (int rc = njp_launch_post(a, b.N, post2, s)) return rc;
+        if (int rc = nj_timing_mark(b.kt, sample, s)) return rc;
+        return nj_timing_mark(b.kt, sample, s);
     }
     // Unit-sharded mode (every rank holds the whole position-space matrix): a unit belongs to rank
     // (strip * G16 + group) mod world for good.  Each rank tests and scans only its own units -- a unit that
     // holds the winner always survives its owner's test, whatever the other ranks' bounds are -- so the unit
     // bounds stay private to their owner and ONE small all-gather per iteration (the unit records) is the
     // only exchange; the new-row blocks, select + merge + update run replicated.
-    const int gr = njp_grid_rank(q);
-    const int v0 = q.sh_virtual ? 0 : q.sh_rank, v1 = q.sh_virtual ? q.sh_world : q.sh_rank + 1;
-    for (int v = v0; v < v1; ++v)
-        if (int rc = njp_launch_scan(b, s, v, v == v0)) return rc;
+    const int v0 = njp_first_rank(q), v1 = njp_last_rank(q);
+    for (int v = v0; v < v1; ++v) {
+        NjpArgs a = njp_args(b, v);
+        a.do_rows = v == v0 ? 1 : 0;
+        if (int rc = njp_launch_scan(a, s)) return rc;
+    }
     if (!q.sh_virtual) {
         if (!q.gather) { set_error("njp: unit-sharded mode without a gather callback"); return DPR_ERR_STATE; }
-        if (int rc = q.gather(q.gather_ctx, b.partials, sizeof(NjRecord) * (size_t)gr, s)) return rc;
+        if (int rc = q.gather(q.gather_ctx, b.partials, sizeof(NjRecord) * (size_t)njp_grid_rank(q), s)) return rc;
     }
     // (virtual ranks: the update runs once, with the first rank's tests; the other ranks' tests follow in launches of
     // their own -- they read only what the update leaves alone: the current U buffer, rows x and y, the scan records)
-    for (int v = v0; v < v1; ++v)
-        if (int rc = njp_launch_post(b, s, v, v == v0)) return rc;
+    for (int v = v0; v < v1; ++v) {
+        NjpArgs a = njp_args(b, v);
+        a.do_update = v == v0 ? 1 : 0;
+        if (int rc = njp_launch_post(a, b.N, post2, s)) return rc;
+    }
     return DPR_OK;
 }
 
-// enqueue `todo` iterations starting at iteration it0.  The kernels of an iteration take no per-iteration
-// arguments, so kGraphIters iterations are captured once into a hipGraph and replayed; iterations beyond
-// it_limit are no-ops.  Afterwards the node in quarantine is materialised (row sum, matrix row).
-// (NjPruned::graph_iters, default 32; DPR_NJ_GRAPH_ITERS at njp_build)
+// The kernels of an iteration take no per-iteration arguments, so q.graph_iters iterations (default 32; DPR_NJ_GRAPH_ITERS at
+// build) are captured once per epoch into a hipGraph and replayed; iterations beyond it_limit are no-ops.  `enqueue` enqueues one
+// iteration on s.  A failure leaves q.graph null.
+int njp_capture_graph(NjPruned& q, hipStream_t s, const std::function<int()>& enqueue)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    ScopedGraph g;
+    DPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = DPR_OK;
+    for (int k = 0; k < q.graph_iters && rc == DPR_OK; ++k) rc = enqueue();
+    hipError_t e = hipStreamEndCapture(s, g.put());
+    if (rc != DPR_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
+    e = hipGraphInstantiate(&q.graph, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) { q.graph = nullptr; return hip_fail(e, "hipGraphInstantiate"); }
+    if (log_level("epoch") > 0)
+        std::fprintf(stderr, "[njp] graph capture + instantiate (P=%lld): %.2f ms\n", (long long)q.P,
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return DPR_OK;
+}
 
+// enqueue `todo` iterations starting at iteration it0 (whole graphs, then an eager tail).  Afterwards the node in quarantine
+// is materialised (row sum, matrix row).
 static int njp_run_segment(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t s)
 {
     NjPruned& q = b.pr;
@@ -1992,53 +1991,30 @@ static int njp_run_segment(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t 
     DPR_HIP(hipMemcpyAsync(&b.st->it_limit, &limit, sizeof(int64_t), hipMemcpyHostToDevice, s));
     DPR_HIP(hipStreamSynchronize(s));   // `limit` is a stack variable
     if (todo <= 0) return DPR_OK;
-    const int v0 = q.sh_world > 1 && !q.sh_virtual ? q.sh_rank : 0;
-    const int v1 = q.sh_world > 1 ? (q.sh_virtual ? q.sh_world : q.sh_rank + 1) : 1;
+    const int v0 = njp_first_rank(q), v1 = njp_last_rank(q);
     if (q.fresh) {      // first scan of an epoch: every unit
-        for (int v = v0; v < v1; ++v) {
-            NjpArgs a = njp_args(b, v);
-            if (a.ntest > 0) hipLaunchKernelGGL(njp_list_all_kernel, dim3((unsigned)a.ntest), dim3(kThreads), 0, s, a);
-        }
-        DPR_HIP(hipGetLastError());
+        for (int v = v0; v < v1; ++v)
+            if (int rc = njp_launch_list_all(njp_args(b, v), s)) return rc;
         if (njp_use_post2(q)) {
             // the maxima the first post launch of the epoch reads: the row sums as they stand (buffer of the current iteration)
             const int64_t S2 = (q.P + kTileCols - 1) / kTileCols + 2;
             const int par = (int)(it0 & 1);
             hipLaunchKernelGGL(njp_t2_init_kernel, dim3((unsigned)((q.P + kTileCols - 1) / kTileCols)), dim3(kThreads), 0, s,
-                               (const double*)(q.U + (it0 & 1) * q.vstride), q.P, q.t2_rmax + par * 32 * S2, q.t2_cmax + par * 4 * S2);
+                               (const double*)njp_current_u(q, it0), q.P, q.t2_rmax + par * 32 * S2, q.t2_cmax + par * 4 * S2);
             DPR_HIP(hipGetLastError());
         }
         q.fresh = false;
     }
     const bool timing = b.kt && b.kt->stride > 0 && q.sh_world <= 1;
-    const int kGraphIters = q.graph_iters;
-    const bool use_graph = q.sh_world <= 1 && todo >= kGraphIters && !timing;      // (DPR_NJ_GRAPH_ITERS above `todo`: eager launches)
-    if (use_graph && !q.graph) {
-        const auto tg0 = std::chrono::steady_clock::now();
-        ScopedGraph g;
-        DPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = DPR_OK;
-        for (int k = 0; k < kGraphIters && rc == DPR_OK; ++k) rc = njp_enqueue_iteration(b, s);
-        hipError_t e = hipStreamEndCapture(s, g.put());
-        if (rc != DPR_OK) return rc;
-        if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
-        DPR_HIP(hipGraphInstantiate(&q.graph, g, nullptr, nullptr, 0));
-        g.reset();
-        if (log_level("epoch") > 0)
-            std::fprintf(stderr, "[njp] graph capture + instantiate (P=%lld): %.2f ms\n", (long long)q.P,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg0).count());
-    }
+    const bool use_graph = q.sh_world <= 1 && todo >= q.graph_iters && !timing;      // (DPR_NJ_GRAPH_ITERS above `todo`: eager launches)
+    if (use_graph && !q.graph)
+        if (int rc = njp_capture_graph(q, s, [&] { return njp_enqueue_iteration(b, s); })) return rc;
     int64_t done = 0;
     if (use_graph)
-        for (; done + kGraphIters <= todo; done += kGraphIters) DPR_HIP(hipGraphLaunch(q.graph, s));
+        for (; done + q.graph_iters <= todo; done += q.graph_iters) DPR_HIP(hipGraphLaunch(q.graph, s));
     for (; done < todo; ++done)
         if (int rc = njp_enqueue_iteration(b, s, timing && (it0 + done) % b.kt->stride == 0)) return rc;
-    {
-        NjpArgs a = njp_args(b, v0);
-        hipLaunchKernelGGL((njp_finish_kernel<false>), dim3((unsigned)a.nrb), dim3(kThreads), 0, s, a);
-        DPR_HIP(hipGetLastError());
-    }
-    return DPR_OK;
+    return njp_launch_finish(njp_args(b, v0), s);
 }
 
 static const char* const kNjpKernelNames[] = { "njp_scan_kernel", "njp_post_kernel", "(empty event pair)", "" };
@@ -2092,15 +2068,33 @@ int njp_shape(const NjPruned& q, int64_t* positions, int* row_groups, int* strip
     return DPR_OK;
 }
 
+// ---- epoch schedule (njp_run, njr_run) ----------------------------------------------------------------------------
+constexpr int64_t kEpochPct = 80;      // rebuild once n <= 80 % of the epoch's positions (85 / 90 measured: DESIGN.md section 4.4)
+// epochs smaller than this are not rebuilt (read at every run call: tests change it inside one process)
+int64_t njp_epoch_min()
+{
+    const char* e = std::getenv("DPR_NJ_EPOCH_MIN");
+    return e ? std::atoll(e) : 2048;
+}
+// With n active nodes in an epoch of P positions and `left` iterations to go: true = rebuild the epoch now; false = run *seg
+// iterations (up to the point where the active size reaches the rebuild target) and ask again.
+bool njp_epoch_due(int64_t P, int64_t n, int64_t left, int64_t epoch_min, int64_t* seg)
+{
+    *seg = left;
+    if (epoch_min <= 0 || P < epoch_min) return false;
+    const int64_t target = P * kEpochPct / 100;
+    if (n <= target && n >= 3) return true;
+    if (n - target < left) *seg = n - target;
+    return false;
+}
+
 // enqueue `todo` iterations starting at iteration it0, in epochs: whenever the active size has dropped to
-// pct % of the epoch's positions (and the epoch is large enough to matter) the position space is rebuilt; with the
+// kEpochPct % of the epoch's positions (and the epoch is large enough to matter) the position space is rebuilt; with the
 // adaptive plan on, the listing rate is watched and the run handed over to the streaming loop (and back) as described in
 // dpr_internal.hpp
 int njp_run(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t s)
 {
-    const char* e_min = std::getenv("DPR_NJ_EPOCH_MIN");
-    const int64_t epoch_min = e_min ? std::atoll(e_min) : 2048;   // epochs smaller than this are not rebuilt
-    const int64_t pct = 80;           // rebuild once n <= pct% of the epoch's positions (85 / 90 measured: DESIGN.md section 4.4)
+    const int64_t epoch_min = njp_epoch_min();
     NjPruned& q = b.pr;
     int64_t it = it0, left = todo;
     if (left <= 0) return q.slots_mode ? DPR_OK : njp_run_segment(b, it0, 0, s);
@@ -2118,25 +2112,20 @@ int njp_run(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t s)
             it += seg; left -= seg;
             continue;
         }
-        const int64_t P = q.P;
         int64_t seg = left;
-        if (epoch_min > 0 && P >= epoch_min) {
-            const int64_t target = P * pct / 100;
-            if (n <= target && n >= 3) {
-                DPR_HIP(hipStreamSynchronize(s));
-                const auto t0 = std::chrono::steady_clock::now();
-                bool rebuilt = false;
-                if (int rc = njp_rebuild_epoch(b, s, &rebuilt)) return rc;
-                // not rebuilt: the run has no candidate left (status != 0: e.g. only rows with NaN row sums are still active -- a NaN
-                // distance makes the row sums of ITS two rows NaN, those rows never win and stay to the end) and every queued
-                // kernel is a no-op -- stop here, dpr_nj_run reports DPR_ERR_NOCAND
-                if (!rebuilt) return DPR_OK;
-                if (log_level("epoch") > 0)
-                    std::fprintf(stderr, "[njp] epoch rebuild at n=%lld: %.2f ms\n", (long long)n,
-                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-                continue;
-            }
-            if (n - target < seg) seg = n - target;
+        if (njp_epoch_due(q.P, n, left, epoch_min, &seg)) {
+            DPR_HIP(hipStreamSynchronize(s));
+            const auto t0 = std::chrono::steady_clock::now();
+            bool rebuilt = false;
+            if (int rc = njp_rebuild_epoch(b, s, &rebuilt)) return rc;
+            // not rebuilt: the run has no candidate left (status != 0: e.g. only rows with NaN row sums are still active -- a NaN
+            // distance makes the row sums of ITS two rows NaN, those rows never win and stay to the end) and every queued
+            // kernel is a no-op -- stop here, dpr_nj_run reports DPR_ERR_NOCAND
+            if (!rebuilt) return DPR_OK;
+            if (log_level("epoch") > 0)
+                std::fprintf(stderr, "[njp] epoch rebuild at n=%lld: %.2f ms\n", (long long)n,
+                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+            continue;
         }
         // adaptive plan: look at the listing rate after the first graph of an epoch and then every 2 048 iterations
         const bool watch = q.adaptive && q.sh_world <= 1 && q.utot > 0;
@@ -2171,7 +2160,7 @@ int njp_run(NjBuffers& b, int64_t it0, int64_t todo, hipStream_t s)
                 const int64_t na = b.N - it;
                 int64_t pn = na;
                 const int hops = 1 << (q.probe_fail_streak < 4 ? q.probe_fail_streak : 4);
-                for (int h = 0; h < hops; ++h) pn = pn * pct / 100;
+                for (int h = 0; h < hops; ++h) pn = pn * kEpochPct / 100;
                 ++q.probe_fail_streak;
                 q.slots_probe_n = pn;
                 if (int rc = njp_to_slots(b, s)) return rc;

@@ -3,6 +3,8 @@
 #pragma once
 #include "nj_dev.hpp"
 
+#include <functional>
+
 namespace dpr {
 
 constexpr int kUR = 16;  // rows per unit
@@ -184,16 +186,22 @@ __device__ __forceinline__ void njr_scan_publish(const NjpArgs& a, int64_t it, u
     if (tid < a.rs_world) njr_st_flag(njr_win_recflag(a.rs_win[tid], a.rs_lay, par, a.rs_rank), a.rs_seq_base + (unsigned long long)(it + 1));
 }
 
-// host launchers of njp.hip's kernels in their row-sharded instantiations (njr.hip builds the arguments)
-int njp_rs_launch_list_all(const NjpArgs& a, hipStream_t s);
-int njp_rs_launch_scan(const NjpArgs& a, hipStream_t s);
-int njp_rs_launch_post(const NjpArgs& a, int64_t N, hipStream_t s);
-int njp_rs_launch_finish(const NjpArgs& a, hipStream_t s);
+// ---- host side of njp.hip that njr.hip shares (njr.hip builds its own arguments and owns its loop) ------------------------
+// launch layer: one launcher per kernel of the loop; a.rs_world > 0 selects the row-sharded instantiation
+int njp_launch_list_all(const NjpArgs& a, hipStream_t s);
+int njp_launch_scan(const NjpArgs& a, hipStream_t s);                              // with the new-row blocks if a.do_rows
+int njp_launch_post(const NjpArgs& a, int64_t N, bool post2, hipStream_t s);       // with the update blocks (N tips) if a.do_update
+int njp_launch_finish(const NjpArgs& a, hipStream_t s);
+// epoch builds
 int njp_rs_epoch(NjPruned& q, int64_t P, int64_t N, double* Dbuf, int epoch_index, int rs_rank, int rs_world, const void* hdr_from, hipStream_t s);
-int njp_rs_init_vectors(NjPruned& q, const double* U_src, const int32_t* slot_src, int64_t P, int64_t n, int64_t it, hipStream_t s);
-void njp_rs_sort_by_row_sum(std::vector<int32_t>& perm, const std::vector<double>& hU);     // ascending, NaN last, stable
-int64_t njp_vec_len(int64_t N);        // doubles per per-position vector (256-byte multiple)
-int njp_scan_grid_default();           // blocks of the unit scan (DPR_NJP_GRID, default 512)
+int njp_epoch_order(const double* dU, const int32_t* slot_of_pos, int64_t P, int64_t n, std::vector<int32_t>& perm, bool stream_idle, hipStream_t s);   // live positions, ascending row sum, NaN last, stable
+int njp_init_vectors(NjPruned& q, const double* U_src, const int32_t* slot_src, int64_t n, int64_t it, hipStream_t s);
+int njp_put_fresh_state(NjState* d_st, NjState& st, hipStream_t s);                // nothing in quarantine, empty lists
+void njp_plan_from_env(NjPruned& q);                                               // scan_grid (DPR_NJP_GRID), graph_iters (DPR_NJ_GRAPH_ITERS)
+// run schedule
+int64_t njp_epoch_min();                                                           // DPR_NJ_EPOCH_MIN, default 2048
+bool njp_epoch_due(int64_t P, int64_t n, int64_t left, int64_t epoch_min, int64_t* seg);   // rebuild now, or run *seg iterations
+int njp_capture_graph(NjPruned& q, hipStream_t s, const std::function<int()>& enqueue);    // q.graph_iters x enqueue() -> q.graph (null on failure)
 
 // phase stamps (debug; 100 MHz wall clock): thread 0 of every block, kernel k (0 scan, 1 post), slot j
 #define NJP_STAMP(k, j, drain)                                                                             \

@@ -35,7 +35,6 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <numeric>
 
 namespace dpr {
 
@@ -390,17 +389,12 @@ int njr_build(std::vector<NjBuffers*>& ranks, hipStream_t s)
 {
     NjBuffers& b0 = *ranks[0];
     const int64_t N = b0.N;
-    std::vector<double> hU((size_t)N);
-    DPR_HIP(hipMemcpyAsync(hU.data(), b0.U, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, s));
-    DPR_HIP(hipStreamSynchronize(s));
-    std::vector<int32_t> perm((size_t)N);
-    std::iota(perm.begin(), perm.end(), 0);
-    njp_rs_sort_by_row_sum(perm, hU);
+    std::vector<int32_t> perm;
+    if (int rc = njp_epoch_order(b0.U, nullptr, N, N, perm, false, s)) return rc;
     for (NjBuffers* pb : ranks) {
         NjBuffers& b = *pb;
         if (int rc = njr_ensure_buffers(b, s)) return rc;
-        b.pr.scan_grid = njp_scan_grid_default();
-        if (const char* e = std::getenv("DPR_NJ_GRAPH_ITERS")) { const int v = std::atoi(e); if (v >= 1 && v <= 4096) b.pr.graph_iters = v; }
+        njp_plan_from_env(b.pr);
         DPR_HIP(hipMemsetAsync(b.rs.half[1], 0, b.half_bytes, s));
         if (int rc = njp_rs_epoch(b.pr, N, N, b.rs.half[1], 0, b.rs.rank, b.rs.world, nullptr, s)) return rc;
         b.pr.utot0 = b.pr.utot;
@@ -410,7 +404,7 @@ int njr_build(std::vector<NjBuffers*>& ranks, hipStream_t s)
     for (NjBuffers* pb : ranks) {
         NjBuffers& b = *pb;
         if (int rc = njr_permute(b, 0, b.ld, kRowBlock, N, b.pr.D, b.pr.ld, N, s)) return rc;
-        if (int rc = njp_rs_init_vectors(b.pr, b.U, nullptr, N, N, 0, s)) return rc;
+        if (int rc = njp_init_vectors(b.pr, b.U, nullptr, N, 0, s)) return rc;
     }
     DPR_HIP(hipStreamSynchronize(s));                        // `perm` goes out of scope
     return njr_barrier(ranks, s);                            // nobody overwrites the tip-order rows (an odd epoch's buffer) before all pulls are done
@@ -424,16 +418,8 @@ static int njr_rebuild_epoch(std::vector<NjBuffers*>& ranks, hipStream_t s, bool
     DPR_HIP(hipMemcpy(&st, b0.st, sizeof(NjState), hipMemcpyDeviceToHost));
     const int64_t n = st.n, Pold = b0.pr.P;
     if (st.status != 0 || n < 3) return DPR_OK;
-    std::vector<double> hU((size_t)Pold);
-    std::vector<int32_t> hslot((size_t)Pold);
-    DPR_HIP(hipMemcpy(hU.data(), b0.pr.U + (st.it & 1) * b0.pr.vstride, sizeof(double) * (size_t)Pold, hipMemcpyDeviceToHost));
-    DPR_HIP(hipMemcpy(hslot.data(), b0.pr.slot_of_pos, sizeof(int32_t) * (size_t)Pold, hipMemcpyDeviceToHost));
     std::vector<int32_t> perm;
-    perm.reserve((size_t)n);
-    for (int64_t p = 0; p < Pold; ++p)
-        if (hslot[(size_t)p] >= 0) perm.push_back((int32_t)p);
-    if ((int64_t)perm.size() != n) { set_error("njr_rebuild_epoch: live positions do not match the active size"); return DPR_ERR_STATE; }
-    njp_rs_sort_by_row_sum(perm, hU);
+    if (int rc = njp_epoch_order(njp_current_u(b0.pr, st.it), b0.pr.slot_of_pos, Pold, n, perm, true, s)) return rc;
     if (int rc = njr_barrier(ranks, s)) return rc;          // every rank's finish kernel (the last new node's row) is done
     const int e = b0.pr.epoch_index + 1;
     const int src_half = (b0.pr.epoch_index + 1) & 1, dst_half = (e + 1) & 1;      // epoch e lives in half (e + 1) & 1
@@ -441,15 +427,11 @@ static int njr_rebuild_epoch(std::vector<NjBuffers*>& ranks, hipStream_t s, bool
         NjBuffers& b = *pb;
         const NjPruned old = b.pr;          // the old epoch's pointers (read by the kernels below; its slab is the other one)
         DPR_HIP(hipMemsetAsync(b.rs.half[dst_half], 0, b.half_bytes, s));
-        if (int rc = njp_rs_epoch(b.pr, n, b.N, b.rs.half[dst_half], e, b.rs.rank, b.rs.world, nullptr, s)) return rc;
-        b.pr.utot0 = old.utot0; b.pr.scan_grid = old.scan_grid; b.pr.graph_iters = old.graph_iters;
+        if (int rc = njp_rs_epoch(b.pr, n, b.N, b.rs.half[dst_half], e, b.rs.rank, b.rs.world, nullptr, s)) return rc;      // (no range header: post2 is a single-rank kernel)
         DPR_HIP(hipMemcpyAsync(b.pr.perm, perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
         if (int rc = njr_permute(b, src_half, old.ld, kNjrChunk, Pold, b.pr.D, b.pr.ld, n, s)) return rc;
-        if (int rc = njp_rs_init_vectors(b.pr, old.U + (st.it & 1) * old.vstride, old.slot_of_pos, n, n, st.it, s)) return rc;
-        NjState st2 = st;
-        st2.pnew[0] = -1; st2.pnew[1] = -1;
-        for (auto& c : st2.cnt_list) c = 0ull;
-        DPR_HIP(hipMemcpyAsync(b.st, &st2, sizeof(NjState), hipMemcpyHostToDevice, s));
+        if (int rc = njp_init_vectors(b.pr, njp_current_u(old, st.it), old.slot_of_pos, n, st.it, s)) return rc;
+        if (int rc = njp_put_fresh_state(b.st, st, s)) return rc;
         DPR_HIP(hipStreamSynchronize(s));
     }
     if (int rc = njr_barrier(ranks, s)) return rc;          // all pulls out of the old epoch are done before anybody goes on
@@ -466,31 +448,23 @@ static int njr_iteration(std::vector<NjBuffers*>& ranks, hipStream_t s, bool sam
     NjKernelTiming* kt = b0.kt;
     // timing samples: the launches of the FIRST rank held here are bracketed by events (with virtual ranks the other ranks'
     // launches of a phase and the copies that stand in for the collectives fall into the intervals in between)
-    auto mark = [&](size_t r) -> int {
-        if (!sample || r != 0) return DPR_OK;
-        hipEvent_t e = nullptr;
-        DPR_HIP(hipEventCreate(&e));
-        kt->ev.push_back(e);
-        DPR_HIP(hipEventRecord(e, s));
-        return DPR_OK;
-    };
     if (sample) { kt->nk = 5; njp_set_kernel_names(kNjrKernelNames); }
     for (size_t r = 0; r < ranks.size(); ++r) {
-        if (int rc = mark(r)) return rc;
-        if (int rc = njp_rs_launch_scan(njr_args(*ranks[r]), s)) return rc;
-        if (int rc = mark(r)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
+        if (int rc = njp_launch_scan(njr_args(*ranks[r]), s)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
     }
     if (b0.rs.plan == kNjrCollective) { if (int rc = b0.rs.gather(b0.rs.cb_ctx, 0, s)) return rc; ++b0.rs.collectives; }
     for (size_t r = 0; r < ranks.size(); ++r) {
-        if (int rc = mark(r)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
         if (int rc = njr_launch_extract(*ranks[r], s)) return rc;
-        if (int rc = mark(r)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
     }
     if (b0.rs.plan == kNjrCollective) { if (int rc = b0.rs.gather(b0.rs.cb_ctx, 1, s)) return rc; ++b0.rs.collectives; }
     for (size_t r = 0; r < ranks.size(); ++r) {
-        if (int rc = mark(r)) return rc;
-        if (int rc = njp_rs_launch_post(njr_args(*ranks[r]), ranks[r]->N, s)) return rc;
-        if (int rc = mark(r)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
+        if (int rc = njp_launch_post(njr_args(*ranks[r]), ranks[r]->N, false, s)) return rc;
+        if (int rc = nj_timing_mark(kt, sample && r == 0, s)) return rc;
     }
     b0.rs.launches += 3;
     return DPR_OK;
@@ -504,7 +478,7 @@ static int njr_run_segment(std::vector<NjBuffers*>& ranks, int64_t it0, int64_t 
     if (todo <= 0) return DPR_OK;
     for (NjBuffers* pb : ranks) {
         if (!pb->pr.fresh) continue;
-        if (int rc = njp_rs_launch_list_all(njr_args(*pb), s)) return rc;
+        if (int rc = njp_launch_list_all(njr_args(*pb), s)) return rc;
         pb->pr.fresh = false;
     }
     NjBuffers& b0 = *ranks[0];
@@ -514,16 +488,7 @@ static int njr_run_segment(std::vector<NjBuffers*>& ranks, int64_t it0, int64_t 
     const int gi = b0.pr.graph_iters;
     const bool use_graph = ranks.size() == 1 && b0.rs.plan == kNjrMailbox && todo >= gi && !timing;
     if (use_graph && !b0.pr.graph) {
-        ScopedGraph g;
-        DPR_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = DPR_OK;
-        for (int k = 0; k < gi && rc == DPR_OK; ++k) rc = njr_iteration(ranks, s, false);
-        hipError_t e = hipStreamEndCapture(s, g.put());
-        if (rc != DPR_OK) return rc;
-        if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
-        e = hipGraphInstantiate(&b0.pr.graph, g, nullptr, nullptr, 0);
-        g.reset();
-        if (e != hipSuccess) { b0.pr.graph = nullptr; return hip_fail(e, "hipGraphInstantiate"); }
+        if (int rc = njp_capture_graph(b0.pr, s, [&] { return njr_iteration(ranks, s, false); })) return rc;
         b0.rs.launches -= 3 * gi;      // (captured, not launched)
     }
     int64_t done = 0;
@@ -532,33 +497,26 @@ static int njr_run_segment(std::vector<NjBuffers*>& ranks, int64_t it0, int64_t 
     for (; done < todo; ++done)
         if (int rc = njr_iteration(ranks, s, timing && (it0 + done) % b0.kt->stride == 0)) return rc;
     for (NjBuffers* pb : ranks)
-        if (int rc = njp_rs_launch_finish(njr_args(*pb), s)) return rc;
+        if (int rc = njp_launch_finish(njr_args(*pb), s)) return rc;
     return DPR_OK;
 }
 
-// enqueue `todo` iterations starting at it0, in epochs (njp_run's rule: rebuild once the active size is down to pct % of the
-// epoch's positions).  The adaptive hand-over to the streaming loop is a single-GPU plan; here the pruned loop runs throughout.
+// enqueue `todo` iterations starting at it0, in epochs (njp_run's schedule: njp_epoch_due).  The adaptive hand-over to the
+// streaming loop is a single-GPU plan; here the pruned loop runs throughout.
 int njr_run(std::vector<NjBuffers*>& ranks, int64_t it0, int64_t todo, hipStream_t s)
 {
-    const char* e_min = std::getenv("DPR_NJ_EPOCH_MIN");
-    const int64_t epoch_min = e_min ? std::atoll(e_min) : 2048;
-    const int64_t pct = 80;
+    const int64_t epoch_min = njp_epoch_min();
     NjBuffers& b0 = *ranks[0];
     int64_t it = it0, left = todo;
     if (left <= 0) return njr_run_segment(ranks, it0, 0, s);
     while (left > 0) {
-        const int64_t n = b0.N - it, P = b0.pr.P;
         int64_t seg = left;
-        if (epoch_min > 0 && P >= epoch_min) {
-            const int64_t target = P * pct / 100;
-            if (n <= target && n >= 3) {
-                DPR_HIP(hipStreamSynchronize(s));
-                bool rebuilt = false;
-                if (int rc = njr_rebuild_epoch(ranks, s, &rebuilt)) return rc;
-                if (!rebuilt) return DPR_OK;        // no candidate left: every queued kernel is a no-op, dpr_nj_run reports it
-                continue;
-            }
-            if (n - target < seg) seg = n - target;
+        if (njp_epoch_due(b0.pr.P, b0.N - it, left, epoch_min, &seg)) {
+            DPR_HIP(hipStreamSynchronize(s));
+            bool rebuilt = false;
+            if (int rc = njr_rebuild_epoch(ranks, s, &rebuilt)) return rc;
+            if (!rebuilt) return DPR_OK;        // no candidate left: every queued kernel is a no-op, dpr_nj_run reports it
+            continue;
         }
         if (int rc = njr_run_segment(ranks, it, seg, s)) return rc;
         it += seg; left -= seg;
