@@ -130,6 +130,10 @@ def load_library():
     L.dpr_get_exact_state.argtypes = [C.c_void_p, c_i32p, c_i32p]
     L.dpr_dc_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
                              c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p]
+    L.dpr_place_fixed_set.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p]
+    L.dpr_place_fixed_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_i32p, c_f64p, c_f64p]
+    L.dpr_ctx_set_place_fixed_batch.argtypes = [C.c_void_p, C.c_int64]
+    L.dpr_get_place_fixed_timing.argtypes = [C.c_void_p, c_f64p, c_f64p]
     L.dpr_njp_unit_owner.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     L.dpr_dc_query_share.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dpr_dc_deal_clusters.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int, c_i32p]
@@ -516,6 +520,34 @@ class Dipper:
                              groups=int(counts[3]), jobs=int(counts[4]), backbone_ms=float(ms[0]),
                              assign_ms=float(ms[1]), cluster_ms=float(ms[2])))
         return st
+
+    def place_fixed_set(self, m, n, state):
+        """dpr_place_fixed_set: the backbone of m tips (adjacency arrays of `state`, sized for n tips) becomes the context's
+        fixed backbone"""
+        st = {k: np.ascontiguousarray(state[k], dtype=np.float64 if k == "len" else np.int32) for k in ("head", "e", "nxt", "belong", "len")}
+        assert st["head"].size >= 2 * n and all(st[k].size >= 8 * n for k in ("e", "nxt", "belong", "len"))
+        _chk(self.L, self.L.dpr_place_fixed_set(self.h, m, n, _p(st["head"], c_i32p), _p(st["e"], c_i32p), _p(st["nxt"], c_i32p),
+                                                _p(st["belong"], c_i32p), _p(st["len"], c_f64p)))
+        self._pfix_nq = n - m
+
+    def place_fixed_run(self, source, dist_type=1, k=15):
+        """dpr_place_fixed_run: (slot, frac, add) of every query against the context's current input"""
+        nq = max(getattr(self, "_pfix_nq", 1), 1)      # (never set: one entry, the library reports the state error)
+        slot = np.full(nq, -2, np.int32)
+        frac = np.zeros(nq, np.float64)
+        add = np.zeros(nq, np.float64)
+        _chk(self.L, self.L.dpr_place_fixed_run(self.h, source, dist_type, k, _p(slot, c_i32p), _p(frac, c_f64p), _p(add, c_f64p)))
+        return slot, frac, add
+
+    def set_place_fixed_batch(self, queries):
+        _chk(self.L, self.L.dpr_ctx_set_place_fixed_batch(self.h, queries))
+
+    def place_fixed_timing(self):
+        """(distance blocks, scan + reduce) of the last place_fixed_run in milliseconds"""
+        a = C.c_double()
+        b = C.c_double()
+        _chk(self.L, self.L.dpr_get_place_fixed_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def warm_graphs(self):
         _chk(self.L, self.L.dpr_warm_graphs(self.h))

@@ -171,6 +171,7 @@ int dpr_destroy(dpr_ctx* c)
     mash_free(c->mash);
     place_free(c->place);
     exact_free(c->exact);
+    pfix_free(c->pfix);
     tbe_free(c->tbe);
     if (c->place_trace) (void)hipFree(c->place_trace);
     if (c->packed_lower) (void)hipFree(c->packed_lower);

@@ -1,5 +1,5 @@
 // Shared by the translation units that implement the C ABI (ctx.hip: context, inputs, hooks; ctx_comm.hip: RCCL, peer
-// windows, exchanges; ctx_nj.hip: distance matrix + NJ plans; ctx_place.hip: placement, exact mode, divide-and-conquer).
+// windows, exchanges; ctx_nj.hip: distance matrix + NJ plans; ctx_place.hip: placement, exact mode, divide-and-conquer, fixed-backbone placement).
 #pragma once
 #include "dpr_internal.hpp"
 
@@ -46,6 +46,8 @@ struct dpr_ctx {
     dpr::MashBuffers mash;
     dpr::PlaceBuffers place;
     dpr::ExactBuffers exact;
+    dpr::PlaceFixed pfix;            // dpr_place_fixed_set: the fixed backbone's edge table and the buffers of dpr_place_fixed_run
+    double pfix_ms[2] = { 0, 0 };    // distance blocks, scan + reduce of the last dpr_place_fixed_run
     dpr::TbeBuffers tbe;
     int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip

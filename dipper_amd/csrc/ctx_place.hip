@@ -1,5 +1,6 @@
 // C ABI, tree builders that place tips: k-closest placement (batches of distance rows, overlap policy), exact placement mode,
-// divide-and-conquer; dpr_place_run, dpr_place_exact_run, dpr_dc_run and their getters.
+// divide-and-conquer, fixed-backbone placement; dpr_place_run, dpr_place_exact_run, dpr_dc_run, dpr_place_fixed_set / _run and their
+// getters.
 #include "ctx_internal.hpp"
 
 using namespace dpr;
@@ -17,6 +18,29 @@ static int check_source(dpr_ctx* c, const char* fn, int source, int k, int64_t n
     } else if (source == DPR_SRC_MATRIX) {
         if (!c->packed_lower || c->n_input != n) { set_error(f + ": call dpr_set_matrix_lower first"); return DPR_ERR_STATE; }
     } else { set_error(f + ": unknown source"); return DPR_ERR_ARG; }
+    return DPR_OK;
+}
+
+// c->place for n tips again; the fixed backbone of dpr_place_fixed_set lived in the old arrays
+static int rebuild_place(dpr_ctx* c, int64_t n, int64_t M = 0)
+{
+    c->pfix.valid = false;
+    return place_alloc(c->place, n, M);
+}
+
+// An imported backbone must be a rooted binary tree: `first` tips, first - 1 internal nodes, 2 first - 2 edges = the slots
+// [0, 4 first - 4) all in use.  The reference's scan reads head[e[slot]] of every slot below 4 num - 4
+// (src/placement_close_k.cu:325-338): an unused slot (e = belong = -1: a trifurcating root, a polytomy) is an
+// out-of-bounds read there; here it is an error, since the edge records (one per undirected edge, dense: 2 num - 2 after
+// num tips) have no place for a missing edge either (advisor, round 5).
+static int check_backbone_slots(const char* fn, int64_t first, const int32_t* e, const int32_t* belong)
+{
+    for (int64_t s = 0; s < 4 * first - 4; ++s)
+        if (e[s] < 0 || belong[s] < 0) {
+            set_error(std::string(fn) + ": the backbone is not a rooted binary tree (directed edge slot " + std::to_string(s) + " of " +
+                      std::to_string(4 * first - 4) + " is unused: a trifurcating root or a polytomy); resolve it first");
+            return DPR_ERR_ARG;
+        }
     return DPR_OK;
 }
 
@@ -320,20 +344,8 @@ int dpr_place_run(dpr_ctx* c, int source, int dist_type, int k, int64_t first, i
     if (!c || !head || !e || !nxt || !belong || !len || n < 3 || first < 2 || first > n) { set_error("dpr_place_run: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
     if (int rc = check_source(c, "dpr_place_run", source, k, n)) return rc;
-    if (first > 2) {
-        // An imported backbone must be a rooted binary tree: `first` tips, first - 1 internal nodes, 2 first - 2 edges = the slots
-        // [0, 4 first - 4) all in use.  The reference's scan reads head[e[slot]] of every slot below 4 num - 4
-        // (src/placement_close_k.cu:325-338): an unused slot (e = belong = -1: a trifurcating root, a polytomy) is an
-        // out-of-bounds read there; here it is an error, since the edge records (one per undirected edge, dense: 2 num - 2 after
-        // num tips) have no place for a missing edge either (advisor, round 5).
-        for (int64_t s = 0; s < 4 * first - 4; ++s)
-            if (e[s] < 0 || belong[s] < 0) {
-                set_error("dpr_place_run: the backbone is not a rooted binary tree (directed edge slot " + std::to_string(s) + " of " +
-                          std::to_string(4 * first - 4) + " is unused: a trifurcating root or a polytomy); resolve it first");
-                return DPR_ERR_ARG;
-            }
-    }
-    if (int rc = place_alloc(c->place, n)) return rc;
+    if (first > 2) { if (int rc = check_backbone_slots("dpr_place_run", first, e, belong)) return rc; }
+    if (int rc = rebuild_place(c, n)) return rc;
     PlaceBuffers& p = c->place;
     if (int rc = reset_place_trace(c, n)) return rc;
     DPR_HIP(hipMemsetAsync(p.misc + 2, 0, 2 * sizeof(int32_t), c->stream));      // fallback counters of the four-tip launches (dpr_get_place_walks)
@@ -364,7 +376,7 @@ static int place_exact_attempt(dpr_ctx* c, int source, int dist_type, int k, int
     if (!c || !head || !e || !nxt || !belong || !len || n < 3) { set_error("dpr_place_exact_run: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
     if (int rc = check_source(c, "dpr_place_exact_run", source, k, n)) return rc;
-    if (int rc = place_alloc(c->place, n)) return rc;
+    if (int rc = rebuild_place(c, n)) return rc;
     if (int rc = exact_alloc(c->exact, n)) return rc;
     PlaceBuffers& p = c->place;
     ExactBuffers& x = c->exact;
@@ -446,7 +458,7 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
     }
     if (int rc = check_source(c, "dpr_dc_run", source, k, n)) return rc;
     const int64_t B = backbone;
-    if (int rc = place_alloc(c->place, n, B)) return rc;
+    if (int rc = rebuild_place(c, n, B)) return rc;
     PlaceBuffers& p = c->place;
     if (int rc = reset_place_trace(c, n)) return rc;
     ScopedEvent ev[4];
@@ -629,6 +641,116 @@ int dpr_get_place_state(dpr_ctx* c, int32_t* cid, double* cdis, double* trace)
     if (cid) DPR_HIP(hipMemcpy(cid, c->place.cid, sizeof(int32_t) * (size_t)(40 * n), hipMemcpyDeviceToHost));
     if (cdis) DPR_HIP(hipMemcpy(cdis, c->place.cdis, sizeof(double) * (size_t)(40 * n), hipMemcpyDeviceToHost));
     if (trace) DPR_HIP(hipMemcpy(trace, c->place_trace, sizeof(double) * (size_t)(3 * n), hipMemcpyDeviceToHost));
+    return DPR_OK;
+}
+
+// ---- independent placement on a fixed backbone (pfix.hip) -------------------------------------------------------------
+int dpr_place_fixed_set(dpr_ctx* c, int64_t m, int64_t n, const int32_t* head, const int32_t* e, const int32_t* nxt,
+                        const int32_t* belong, const double* len)
+{
+    if (!c || !head || !e || !nxt || !belong || !len || m < 3 || m >= n) { set_error("dpr_place_fixed_set: bad argument (3 <= m < n)"); return DPR_ERR_ARG; }
+    DPR_HIP(hipSetDevice(c->device));
+    if (int rc = check_backbone_slots("dpr_place_fixed_set", m, e, belong)) return rc;
+    if (int rc = rebuild_place(c, n)) return rc;
+    // (the arrays are only read: host -> device)
+    if (int rc = copy_adjacency(c, n, true, const_cast<int32_t*>(head), const_cast<int32_t*>(e), const_cast<int32_t*>(nxt),
+                                const_cast<int32_t*>(belong), const_cast<double*>(len))) return rc;
+    if (int rc = place_import_backbone(c->place, m, c->stream)) return rc;
+    if (int rc = pfix_set(c->pfix, c->place, m, c->stream)) return rc;
+    DPR_HIP(hipStreamSynchronize(c->stream));
+    return DPR_OK;
+}
+
+int dpr_ctx_set_place_fixed_batch(dpr_ctx* c, int64_t queries)
+{
+    if (!c || queries < 0 || queries > 65536) { set_error("dpr_ctx_set_place_fixed_batch: 0 (the rule of dpr_dc_run) .. 65536 queries"); return DPR_ERR_ARG; }
+    c->pfix.batch = queries;
+    return DPR_OK;
+}
+
+int dpr_place_fixed_run(dpr_ctx* c, int source, int dist_type, int k, int32_t* slot, double* frac, double* add)
+{
+    if (!c || !slot || !frac || !add) { set_error("dpr_place_fixed_run: bad argument"); return DPR_ERR_ARG; }
+    PlaceFixed& f = c->pfix;
+    if (!f.valid) { set_error("dpr_place_fixed_run: call dpr_place_fixed_set first (a placement run since then has replaced the backbone)"); return DPR_ERR_STATE; }
+    DPR_HIP(hipSetDevice(c->device));
+    if (source != DPR_SRC_MSA && source != DPR_SRC_MASH) { set_error("dpr_place_fixed_run: input must be unaligned or aligned sequences"); return DPR_ERR_ARG; }
+    const int64_t n = f.n, m = f.m, nq = n - m;
+    if (int rc = check_source(c, "dpr_place_fixed_run", source, k, n)) return rc;
+    const bool real = comm_real(c);
+    const int W = real ? c->world : 1, rank = real ? c->rank : 0;
+    // contiguous query shares as dpr_dc_query_share: rank r takes [m + r * share, m + (r + 1) * share) below n, and its results are
+    // segment r of the all-gather
+    const int64_t share = ((nq + W - 1) / W + 255) / 256 * 256;
+    int64_t q0 = 0, q1 = 0;
+    dc_query_share(n, m, rank, W, &q0, &q1);
+    // queries per batch: the rule of dpr_dc_run (the block of distances to all backbone tips stays below 2 GiB)
+    int64_t Q = ((int64_t)1 << 31) / (8 * m) / 256 * 256;
+    if (Q < 256) Q = 256;
+    if (Q > 8192) Q = 8192;
+    if (Q > (nq + 255) / 256 * 256) Q = (nq + 255) / 256 * 256;
+    if (f.batch > 0) Q = f.batch;
+    if ((size_t)(m * Q) > f.dT_cap) {
+        if (f.dT) { (void)hipFree(f.dT); f.dT = nullptr; f.dT_cap = 0; }
+        DPR_HIP(hipMalloc(&f.dT, sizeof(double) * (size_t)(m * Q)));
+        f.dT_cap = (size_t)(m * Q);
+    }
+    if ((size_t)(share * W) > f.out_cap) {
+        void* old[] = { f.slot, f.frac, f.add };
+        for (void* q : old)
+            if (q) (void)hipFree(q);
+        f.slot = nullptr; f.frac = nullptr; f.add = nullptr; f.out_cap = 0;
+        DPR_HIP(hipMalloc(&f.slot, sizeof(int32_t) * (size_t)(share * W)));
+        DPR_HIP(hipMalloc(&f.frac, sizeof(double) * (size_t)(share * W)));
+        DPR_HIP(hipMalloc(&f.add, sizeof(double) * (size_t)(share * W)));
+        f.out_cap = (size_t)(share * W);
+    }
+    const bool carry = std::getenv("DPR_PFIX_CARRY") != nullptr && std::atoi(std::getenv("DPR_PFIX_CARRY")) != 0;
+    const RowSource src{ c, source, dist_type };
+    std::vector<ScopedEvent> ev;      // per batch: start, distances done, placed
+    auto mark = [&]() -> int { ev.emplace_back(); DPR_HIP(hipEventCreate(ev.back().put())); DPR_HIP(hipEventRecord(ev.back(), c->stream)); return DPR_OK; };
+    auto run = [&]() -> int {
+        if (real) {      // (segments of other ranks' trailing, unused entries are gathered too: defined)
+            DPR_HIP(hipMemsetAsync(f.slot + rank * share, 0xff, sizeof(int32_t) * (size_t)share, c->stream));
+            DPR_HIP(hipMemsetAsync(f.frac + rank * share, 0, sizeof(double) * (size_t)share, c->stream));
+            DPR_HIP(hipMemsetAsync(f.add + rank * share, 0, sizeof(double) * (size_t)share, c->stream));
+        }
+        for (int64_t i0 = q0; i0 < q1; i0 += Q) {
+            const int64_t nr = q1 - i0 < Q ? q1 - i0 : Q, o = i0 - m;
+            if (int rc = mark()) return rc;
+            if (int rc = src.fill(i0, nr, f.dT, Q, m, c->stream, true)) return rc;
+            if (int rc = mark()) return rc;
+            if (int rc = pfix_place(f, f.dT, Q, (int)nr, f.slot + o, f.frac + o, f.add + o, carry, c->stream)) return rc;
+            if (int rc = mark()) return rc;
+        }
+        if (real) {
+            if (int rc = comm_all_gather(c, f.slot + rank * share, f.slot, sizeof(int32_t) * (size_t)share, c->stream)) return rc;
+            if (int rc = comm_all_gather(c, f.frac + rank * share, f.frac, sizeof(double) * (size_t)share, c->stream)) return rc;
+            if (int rc = comm_all_gather(c, f.add + rank * share, f.add, sizeof(double) * (size_t)share, c->stream)) return rc;
+        }
+        DPR_HIP(hipMemcpyAsync(slot, f.slot, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+        DPR_HIP(hipMemcpyAsync(frac, f.frac, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+        DPR_HIP(hipMemcpyAsync(add, f.add, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+        return DPR_OK;
+    };
+    const int rc = run();
+    const hipError_t se = hipStreamSynchronize(c->stream);      // (the stream is idle before the events are released)
+    if (rc) return rc;
+    DPR_HIP(se);
+    c->pfix_ms[0] = c->pfix_ms[1] = 0;
+    for (size_t i = 0; i + 2 < ev.size(); i += 3)
+        for (int k2 = 0; k2 < 2; ++k2) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[i + (size_t)k2], ev[i + (size_t)k2 + 1]) == hipSuccess) c->pfix_ms[k2] += ms;
+        }
+    return DPR_OK;
+}
+
+int dpr_get_place_fixed_timing(dpr_ctx* c, double* dist_ms, double* scan_ms)
+{
+    if (!c) { set_error("dpr_get_place_fixed_timing: null ctx"); return DPR_ERR_ARG; }
+    if (dist_ms) *dist_ms = c->pfix_ms[0];
+    if (scan_ms) *scan_ms = c->pfix_ms[1];
     return DPR_OK;
 }
 

@@ -600,6 +600,7 @@ int dc_table_build(PlaceBuffers& p, int64_t B, DcTable& t, hipStream_t s);
 void dc_table_free(DcTable& t);
 // dT[c * ldq + q] = distance(query q of the batch, backbone tip c); d_cluster_id[q] = chosen slot
 int dc_assign(DcTable& t, const double* dT, int64_t ldq, int Q, int32_t* d_cluster_id, hipStream_t s);
+int dc_parts_reserve(DcTable& t, int64_t ldq);     // part_add / part_pos for a scan of ldq query columns
 int dc_cluster_phase(PlaceBuffers& p, const int32_t* h_cluster_id, int64_t N, int64_t B, int source, int dist_type,
                      const MsaBuffers* msa, const MashBuffers* mash, double* d_trace, size_t budget_bytes,
                      DcStats* stats, int rank, int world, hipStream_t s);
@@ -609,5 +610,30 @@ void dc_deal_clusters(const int64_t* sizes_desc, int64_t count, int world, int32
 void dc_query_share(int64_t n, int64_t B, int rank, int world, int64_t* q0, int64_t* q1);
 int dc_delta_sub(void* cur, const void* old, int64_t words64, hipStream_t s);   // cur -= old (64-bit words)
 int dc_delta_add(void* cur, const void* old, int64_t words64, hipStream_t s);   // cur += old
+
+// pfix.hip: independent placement of queries on a FIXED backbone (no reference counterpart).  The backbone's edge table (the
+// divide-and-conquer assignment's DcTable: dense records, LDS-sized chunks) is built once by dpr_place_fixed_set and kept; every
+// dpr_place_fixed_run scores all (query, eligible slot) pairs with the arithmetic of calculateBranchLength and returns, per
+// query, the eligible slot with the smallest (pendant length, slot), the position on it and the pendant length.
+struct PlaceFixed {
+    bool valid = false;            // the table belongs to the backbone of the last dpr_place_fixed_set
+    int64_t m = 0, n = 0;          // backbone tips, all tips
+    int64_t batch = 0;             // test hook (dpr_ctx_set_place_fixed_batch): queries per batch, 0 = the rule of dpr_dc_run
+    DcTable tab;
+    int32_t* ent_of_slot = nullptr;    // [4m - 4] table entry of an eligible slot, -1 elsewhere
+    double* part_frac = nullptr;       // [chunks][ldq] positions of the per-chunk minima (the carrying scan only)
+    size_t part_frac_cap = 0;
+    double* dT = nullptr;              // [m][Q] query-minor distance block of a batch
+    size_t dT_cap = 0;
+    int32_t* slot = nullptr;           // [share x ranks] results of the last run
+    double *frac = nullptr, *add = nullptr;
+    size_t out_cap = 0;
+};
+int pfix_set(PlaceFixed& f, PlaceBuffers& p, int64_t m, hipStream_t s);       // p holds the imported backbone and its lists
+void pfix_free(PlaceFixed& f);
+// dT[c * ldq + q] = distance(query q of the batch, backbone tip c); slot / frac / add[q] of the Q queries.  carry: the scan carries
+// the position through its loop instead of the reduce step evaluating the winning entry again (same bits either way)
+int pfix_place(PlaceFixed& f, const double* dT, int64_t ldq, int Q, int32_t* d_slot, double* d_frac, double* d_add, bool carry,
+               hipStream_t s);
 
 }  // namespace dpr

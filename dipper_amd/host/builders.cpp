@@ -402,6 +402,58 @@ void KPlacementDeviceArrays::addQuery(DeviceContext& dev, Param& params)
     printPlaceTiming(dev);
 }
 
+void KPlacementDeviceArrays::placeFixed(DeviceContext& dev, Param& params, const BootstrapOptions& bo, std::vector<std::vector<PlacementRow>>& rows)
+{
+    const size_t nq = (size_t)(numSequences - backboneSize);
+    gpuCheck(dpr_place_fixed_set(dev.ctx, backboneSize, numSequences, h_head.data(), h_e.data(), h_nxt.data(), h_belong.data(), h_len.data()),
+             "dpr_place_fixed_set");
+    std::vector<int32_t> slot(nq);
+    std::vector<double> frac(nq), add(nq);
+    double dist_ms = 0, scan_ms = 0;
+    auto run = [&]() {
+        gpuCheck(dpr_place_fixed_run(dev.ctx, sourceOf(params), (int)params.distanceType, (int)params.kmerSize, slot.data(), frac.data(), add.data()),
+                 "dpr_place_fixed_run");
+        double d = 0, s = 0;
+        dpr_get_place_fixed_timing(dev.ctx, &d, &s);
+        dist_ms += d; scan_ms += s;
+    };
+    // frac is measured from belong[slot]: the child end for the even slot of an edge, the parent end for the odd one
+    auto row_of = [&](size_t q) {
+        const int32_t s = slot[q];
+        if (s < 0) die("ERROR: a query has no placement");
+        return PlacementRow{ s >> 1, 0, (s & 1) ? h_len[(size_t)s] - frac[q] : frac[q], add[q] };
+    };
+    run();
+    rows.assign(nq, {});
+    for (size_t q = 0; q < nq; ++q) rows[q].push_back(row_of(q));
+    std::cerr << "Distance Operation Time " << (long long)dist_ms << " ms\n";
+    std::cerr << "Placement Scan Time " << (long long)scan_ms << " ms\n";
+    if (bo.replicates <= 0) { for (auto& r : rows) r[0].count = 1; return; }
+    dist_ms = scan_ms = 0;
+    for (int64_t r = 0; r < bo.replicates; ++r) {
+        gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, r), "dpr_msa_resample");
+        run();
+        for (size_t q = 0; q < nq; ++q) {
+            const PlacementRow now = row_of(q);
+            std::vector<PlacementRow>& v = rows[q];
+            size_t k = 0;
+            while (k < v.size() && v[k].edge != now.edge) ++k;
+            if (k == v.size()) v.push_back(now);      // (replicates ascend: the lengths of the first one that chose the edge stay)
+            ++v[k].count;
+        }
+    }
+    gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, -1), "dpr_msa_resample");
+    std::cerr << "Bootstrap placements: " << bo.replicates << " replicates, distances " << (long long)dist_ms << " ms, scans " << (long long)scan_ms << " ms\n";
+    for (auto& v : rows) {
+        const int32_t main_edge = v[0].edge;
+        std::sort(v.begin(), v.end(), [main_edge](const PlacementRow& a, const PlacementRow& b) {
+            if (a.count != b.count) return a.count > b.count;
+            if ((a.edge == main_edge) != (b.edge == main_edge)) return a.edge == main_edge;
+            return a.edge < b.edge;
+        });
+    }
+}
+
 void KPlacementDeviceArraysDC::allocateDeviceArraysDC(size_t num, size_t totalNum)
 {
     allocateDeviceArrays(totalNum);          // arrays sized by the total tip count, node ids start there

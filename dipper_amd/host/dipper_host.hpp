@@ -188,6 +188,15 @@ struct Tree {
     int findLeaf(const std::string& name) const;   // node index or -1
 };
 
+struct BootstrapOptions;
+// one row of a query's jplace record: the backbone edge (edge k = the k-th non-root node in post-order of the -t file), the
+// number of bootstrap replicates that chose it, and the attachment point (distal_length from the edge's child end)
+struct PlacementRow {
+    int32_t edge = 0;
+    int64_t count = 0;
+    double distal = 0, pendant = 0;
+};
+
 // k-closest placement (src/mash_placement.cuh:167-197); with exact = true the same host object drives
 // the exact mode of PlacementDeviceArrays (src/mash_placement.cuh:137-165, src/placement.cu): identical
 // adjacency arrays and printTree (src/placement.cu:454-505 == src/placement_close_k.cu:568-643)
@@ -200,6 +209,12 @@ struct KPlacementDeviceArrays {
     void initializeDeviceArrays(const Tree& t);   // backbone -> forward-star adjacency (src/placement_close_k.cu:126-264)
     void findPlacementTree(DeviceContext& dev, Param& params);
     void addQuery(DeviceContext& dev, Param& params);
+    // -o j: every query [backboneSize, numSequences) placed independently on the imported backbone, which stays as it is
+    // (dpr_place_fixed_set / _run).  rows[q]: without --bootstrap the one placement; with it the edges that replicates chose
+    // (their counts; lengths of the lowest-numbered replicate that chose the edge) and the placement from the uploaded
+    // alignment (the main edge: its own lengths, listed even with count 0), ordered by count descending, the main edge first,
+    // then by edge number.
+    void placeFixed(DeviceContext& dev, Param& params, const BootstrapOptions& bo, std::vector<std::vector<PlacementRow>>& rows);
     void printTree(const std::vector<std::string>& name, std::ostream& output_);
 };
 
@@ -275,5 +290,14 @@ std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, c
 // to dpr_split_support, or in place of dpr_transfer_support), one 64-bit sum of moved[] and pairs over the ranks, the report.
 void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& params, const BootstrapOptions& bo,
                                    const uint64_t* packed4, int seqLen, std::vector<std::string>& name, std::ostream& output_);
+
+// ---- jplace output (jplace.cpp; no reference counterpart) ------------------------------------------------------------------
+// jplace version 3 of the placements of placeFixed: the backbone `t` with children in the order of its file, its names, its
+// lengths through the length formatter and {k} after every branch length (k ascends in post-order of the string); fields
+// edge_num, likelihood (always 0: APPLES' convention for distance placements), like_weight_ratio (count / replicates, or 1),
+// distal_length, pendant_length; one record per query in input order (names[backbone + q]); doubles as %.17g.  The metadata name
+// the software, the distance and the bootstrap parameters only: the bytes do not depend on ranks or devices.
+void writeJplace(std::ostream& os, const Tree& t, const std::vector<std::string>& names, const std::vector<std::vector<PlacementRow>>& rows,
+                 const Param& params, const BootstrapOptions& bo);
 
 }  // namespace dipper

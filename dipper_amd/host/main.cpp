@@ -36,6 +36,9 @@ static const char* kHelp =
     "  -o [ --output-format ] arg  Output format:\n"
     "                                t - phylogenetic tree in Newick format (default)\n"
     "                                d - distance matrix in PHYLIP format (coming soon)\n"
+    "                                j - placements in jplace format: every query placed on the\n"
+    "                                    backbone by itself, the backbone unchanged (needs --add -t,\n"
+    "                                    -i m or -i r; with --bootstrap: placement support per edge)\n"
     "  -m [ --algorithm ] arg      Algorithm selection:\n"
     "                                0 - default mode\n"
     "                                1 - force placement\n"
@@ -73,6 +76,8 @@ static const char* kHelp =
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
     "                              -i m -o t with conventional NJ only (-m 2, or -m 0 below 30000)\n"
+    "                              With --add -o j -i m: the queries are placed again under every\n"
+    "                              replicate alignment; like_weight_ratio = share of replicates per edge\n"
     "  --bootstrap-seed arg        Seed of the replicates' column draws (unsigned 64-bit, default 1)\n"
     "  --bootstrap-metric arg      fbp (default): Felsenstein support, the share of replicates that hold\n"
     "                              a split exactly; tbe: transfer bootstrap expectation, one minus the\n"
@@ -239,6 +244,16 @@ int main(int argc, char** argv)
         if (!vm.count(req)) usageError(std::string("the option '--") + req + "' is required but missing");
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
+    // -o j (placements on a fixed backbone): what the arguments alone decide, before any input is read or a GPU touched
+    const bool jplace = strOr(vm, "output-format", "t") == "j";
+    if (jplace) {
+        const std::string in = strOr(vm, "input-format", "r");
+        if (!vm.count("add")) usageError("-o j needs --add and a backbone tree (-t): the queries are placed on that tree");
+        if (in != "m" && in != "r") usageError("-o j needs aligned or unaligned sequences (-i m or -i r)");
+        if (vm.count("bootstrap") && in != "m") usageError("--bootstrap with -o j needs aligned sequences (-i m)");
+        if (vm.count("bootstrap-metric")) usageError("--bootstrap-metric does not apply to -o j (placement support is the share of replicates per edge)");
+        if (vm.count("bootstrap-taxa") || vm.count("bootstrap-taxa-cutoff")) usageError("--bootstrap-taxa does not apply to -o j");
+    }
     // --bootstrap: what the arguments alone decide is checked here, before any input is read or a GPU touched
     BootstrapOptions boot;
     if (vm.count("bootstrap-seed") && !vm.count("bootstrap")) usageError("--bootstrap-seed needs --bootstrap");
@@ -290,9 +305,9 @@ int main(int argc, char** argv)
         }
         const std::string in = strOr(vm, "input-format", "r"), out = strOr(vm, "output-format", "t"), al = strOr(vm, "algorithm", "0");
         if (in != "m") usageError("--bootstrap needs aligned sequences (-i m)");
-        if (vm.count("add")) usageError("--bootstrap is not supported with --add");
-        if (out != "t") usageError("--bootstrap needs tree output (-o t)");
-        if (al == "1" || al == "3") usageError("--bootstrap needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add") && !jplace) usageError("--bootstrap is not supported with --add");
+        if (out != "t" && !jplace) usageError("--bootstrap needs tree output (-o t)");
+        if (!jplace && (al == "1" || al == "3")) usageError("--bootstrap needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
     }
 
     Param params;
@@ -360,7 +375,7 @@ int main(int argc, char** argv)
         // src/tree_generation.cu:252-332
         std::ifstream treeFileStream(strOr(vm, "input-tree", ""));
         if (!treeFileStream) { std::cerr << "ERROR: Unable to open input tree file: " << strOr(vm, "input-tree", "") << "\n"; return 1; }
-        if (!(params.out == "t" && (params.in == "r" || params.in == "m"))) {
+        if (!((params.out == "t" || jplace) && (params.in == "r" || params.in == "m"))) {
             std::cerr << "Adding new sequnces only supported with input aligned and unaligned sequences\n";
             return 1;
         }
@@ -469,6 +484,15 @@ int main(int argc, char** argv)
         kplacementDeviceArrays.allocateDeviceArrays(numSequences, (int)backboneSize);
         kplacementDeviceArrays.initializeDeviceArrays(t);
         if (cliLog()) std::cerr << "  backbone state built at " << ms_since(inputStart) << " ms\n";
+        if (jplace) {
+            std::vector<std::vector<PlacementRow>> rows;
+            kplacementDeviceArrays.placeFixed(dev, params, boot, rows);
+            if (cliLog()) std::cerr << "  queries placed at " << ms_since(inputStart) << " ms\n";
+            writeJplace(*output_, t, names, rows, params, boot);
+            if (cliLog()) std::cerr << "  placements written at " << ms_since(inputStart) << " ms\n";
+            printRankSummary(dev.ctx);
+            return 0;
+        }
         kplacementDeviceArrays.addQuery(dev, params);
         if (cliLog()) std::cerr << "  addQuery done at " << ms_since(inputStart) << " ms\n";
         kplacementDeviceArrays.printTree(names, *output_);

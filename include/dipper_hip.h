@@ -378,6 +378,35 @@ int dpr_dc_deal_clusters(const int64_t *sizes_desc, int64_t count, int world, in
  * phase_ms: backbone tree, cluster assignment, cluster trees (HIP events) */
 int dpr_get_dc_stats(dpr_ctx *ctx, int64_t *counts5, double *phase_ms3);
 
+/* ---- independent placement of queries on a FIXED backbone (no reference counterpart: addQuery, src/placement_close_k.cu:
+ * 858-990, inserts the queries one after the other; findClustersDC, src/divide_and_conquer/placement_close_k.cu:937-1113,
+ * scores them independently but keeps the edge only).  Tips [0, m) are the backbone, tips [m, n) the queries, as for
+ * dpr_place_run with first = m; the backbone is a rooted binary tree in the adjacency form of initializeDeviceArrays
+ * (src/placement_close_k.cu:126-264): edge k = the k-th non-root node in post-order owns slot 2k (child to parent) and 2k + 1.
+ * Every eligible slot s (belong[s] >= e[s]: one per undirected edge) gets, by the arithmetic of calculateBranchLength
+ * (src/placement_close_k.cu:309-358) over the backbone's closest lists, the pendant length `add` and the position `frac` =
+ * distance of the attachment point from node belong[s].  The placement of a query is the eligible slot with the smallest
+ * (add, slot); ineligible slots take no part (no "add = 2" default tuple), add is never NaN.  Where add < 2 it is what
+ * dpr_place_run would do for that query were it the first one added.  The backbone is never modified; no query influences another.
+ * For aligned input the distances to ALL m backbone tips are computed (dpr_dc_run's default stops one short, as the reference). */
+/* Imports the backbone (host arrays sized as for dpr_place_run, only read), builds its closest lists and the edge table, and
+ * keeps them in the context until the next dpr_place_fixed_set, any of dpr_place_run / dpr_place_exact_run / dpr_dc_run
+ * (they rebuild the placement state), or dpr_destroy.  3 <= m < n; a backbone with an unused slot below 4m - 4 (polytomy)
+ * is DPR_ERR_ARG, as for dpr_place_run. */
+int dpr_place_fixed_set(dpr_ctx *ctx, int64_t m, int64_t n, const int32_t *head, const int32_t *e, const int32_t *nxt,
+                        const int32_t *belong, const double *len);
+/* Places all queries [m, n) from the context's CURRENT input: the MSA planes as dpr_set_msa / dpr_msa_resample left them
+ * (DPR_SRC_MSA), or the sketches (DPR_SRC_MASH, k = the sketch k).  slot / frac / add receive n - m entries each, query m + i
+ * at index i.  Queries go through in batches sized as dpr_dc_run sizes them.  Several ranks (dpr_comm_init*): contiguous query
+ * shares as dpr_dc_query_share, the results all-gathered, every rank returns everything.  A second call reuses every
+ * allocation.  DPR_ERR_STATE without a valid dpr_place_fixed_set.  DPR_PFIX_CARRY=1 (A/B aid): the scan carries the position
+ * through its loop instead of the reduce step evaluating the winning entry again -- same bits. */
+int dpr_place_fixed_run(dpr_ctx *ctx, int source, int dist_type, int k, int32_t *slot, double *frac, double *add);
+/* test hook: queries per batch of dpr_place_fixed_run (batch boundaries with a few dozen queries); 0 = dpr_dc_run's rule */
+int dpr_ctx_set_place_fixed_batch(dpr_ctx *ctx, int64_t queries);
+/* distance blocks / scan + reduce of the last dpr_place_fixed_run in milliseconds (HIP events, summed over the batches) */
+int dpr_get_place_fixed_timing(dpr_ctx *ctx, double *dist_ms, double *scan_ms);
+
 /* ---- bootstrap support of NJ trees from aligned sequences (no reference counterpart) ---------------------------------------
  * Replicate r (0-based) of an alignment of L sites draws L columns with replacement (uint64 arithmetic, wrapping):
  *   mix64(z) = splitmix64's finaliser; key_r = mix64(seed ^ mix64(r)); column_t = ((mix64(key_r ^ t) >> 32) * L) >> 32,
