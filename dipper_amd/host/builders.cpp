@@ -423,12 +423,19 @@ void KPlacementDeviceArrays::placeFixed(DeviceContext& dev, Param& params, const
         if (s < 0) die("ERROR: a query has no placement");
         return PlacementRow{ s >> 1, 0, (s & 1) ? h_len[(size_t)s] - frac[q] : frac[q], add[q] };
     };
+    // a placement whose lengths are not finite (a query at +inf from every tip of a backbone: JC at p >= 0.75) cannot be written
+    // as JSON and says nothing: it is left out -- the query as a whole when it is the placement from the uploaded alignment, the
+    // replicate's vote for that query otherwise
+    auto finite = [](const PlacementRow& r) { return std::isfinite(r.pendant) && std::isfinite(r.distal); };
     run();
     rows.assign(nq, {});
-    for (size_t q = 0; q < nq; ++q) rows[q].push_back(row_of(q));
+    for (size_t q = 0; q < nq; ++q) {
+        const PlacementRow r = row_of(q);
+        if (finite(r)) rows[q].push_back(r);
+    }
     std::cerr << "Distance Operation Time " << (long long)dist_ms << " ms\n";
     std::cerr << "Placement Scan Time " << (long long)scan_ms << " ms\n";
-    if (bo.replicates <= 0) { for (auto& r : rows) r[0].count = 1; return; }
+    if (bo.replicates <= 0) { for (auto& r : rows) if (!r.empty()) r[0].count = 1; return; }
     dist_ms = scan_ms = 0;
     for (int64_t r = 0; r < bo.replicates; ++r) {
         gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, r), "dpr_msa_resample");
@@ -436,6 +443,7 @@ void KPlacementDeviceArrays::placeFixed(DeviceContext& dev, Param& params, const
         for (size_t q = 0; q < nq; ++q) {
             const PlacementRow now = row_of(q);
             std::vector<PlacementRow>& v = rows[q];
+            if (v.empty() || !finite(now)) continue;
             size_t k = 0;
             while (k < v.size() && v[k].edge != now.edge) ++k;
             if (k == v.size()) v.push_back(now);      // (replicates ascend: the lengths of the first one that chose the edge stay)
@@ -445,6 +453,7 @@ void KPlacementDeviceArrays::placeFixed(DeviceContext& dev, Param& params, const
     gpuCheck(dpr_msa_resample(dev.ctx, bo.seed, -1), "dpr_msa_resample");
     std::cerr << "Bootstrap placements: " << bo.replicates << " replicates, distances " << (long long)dist_ms << " ms, scans " << (long long)scan_ms << " ms\n";
     for (auto& v : rows) {
+        if (v.empty()) continue;
         const int32_t main_edge = v[0].edge;
         std::sort(v.begin(), v.end(), [main_edge](const PlacementRow& a, const PlacementRow& b) {
             if (a.count != b.count) return a.count > b.count;

@@ -213,7 +213,8 @@ struct KPlacementDeviceArrays {
     // (dpr_place_fixed_set / _run).  rows[q]: without --bootstrap the one placement; with it the edges that replicates chose
     // (their counts; lengths of the lowest-numbered replicate that chose the edge) and the placement from the uploaded
     // alignment (the main edge: its own lengths, listed even with count 0), ordered by count descending, the main edge first,
-    // then by edge number.
+    // then by edge number.  A placement with a length that is not finite is not recorded: rows[q] stays empty when it is the
+    // placement from the uploaded alignment (the query is left out of the file), a replicate's is not counted for that query.
     void placeFixed(DeviceContext& dev, Param& params, const BootstrapOptions& bo, std::vector<std::vector<PlacementRow>>& rows);
     void printTree(const std::vector<std::string>& name, std::ostream& output_);
 };
@@ -296,7 +297,8 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
 // lengths through the length formatter and {k} after every branch length (k ascends in post-order of the string); fields
 // edge_num, likelihood (always 0: APPLES' convention for distance placements), like_weight_ratio (count / replicates, or 1),
 // distal_length, pendant_length; one record per query in input order (names[backbone + q]); doubles as %.17g.  The metadata name
-// the software, the distance and the bootstrap parameters only: the bytes do not depend on ranks or devices.
+// the software, the distance and the bootstrap parameters only: the bytes do not depend on ranks or devices.  A query with no
+// rows has no record; a row with a NaN or an infinity is refused (die) before anything is written: JSON has no token for them.
 void writeJplace(std::ostream& os, const Tree& t, const std::vector<std::string>& names, const std::vector<std::vector<PlacementRow>>& rows,
                  const Param& params, const BootstrapOptions& bo);
 

@@ -2,6 +2,7 @@
 // for phylogenetic placements", version 3 -- what pplacer, EPA-ng and APPLES write and gappa, guppy and iTOL read.
 #include "dipper_host.hpp"
 
+#include <cmath>
 #include <cstdio>
 
 namespace dipper {
@@ -18,8 +19,11 @@ static void putJson(TextBuf& out, const std::string& v)
     out.put('"');
 }
 
+// JSON has no token for a NaN or an infinity (`%.17g` would print the bare words nan / inf, which no reader of jplace accepts):
+// placeFixed hands over finite rows only, and a caller that does not is refused before a byte of the file is written
 static void putDouble(TextBuf& out, double v)
 {
+    if (!std::isfinite(v)) die("ERROR: jplace: a placement with a length that is not finite cannot be written");
     char b[40];
     std::snprintf(b, sizeof b, "%.17g", v);
     out.put(b);
@@ -79,8 +83,11 @@ void writeJplace(std::ostream& os, const Tree& t, const std::vector<std::string>
     putJson(out, jplaceTree(t));
     out.put(",\n\"fields\":[\"edge_num\",\"likelihood\",\"like_weight_ratio\",\"distal_length\",\"pendant_length\"],\n\"placements\":[");
     const size_t backbone = t.m_numLeaves;
+    bool first = true;
     for (size_t q = 0; q < rows.size(); ++q) {
-        out.put(q ? ",\n{\"p\":[" : "\n{\"p\":[");
+        if (rows[q].empty()) continue;      // (a query without a finite placement: placeFixed)
+        out.put(first ? "\n{\"p\":[" : ",\n{\"p\":[");
+        first = false;
         for (size_t k = 0; k < rows[q].size(); ++k) {
             const PlacementRow& r = rows[q][k];
             if (k) out.put(',');

@@ -97,7 +97,7 @@ static const Opt kOpts[] = {
     { "kmer-size", 'k', true }, { "sketch-size", 's', true }, { "distance-type", 'd', true },
     { "add", 'a', false }, { "input-tree", 't', true }, { "help", 'h', false },
     { "seed", 0, true }, { "device", 0, true }, { "gpus", 0, true }, { "devices", 0, true }, { "transport", 0, true },
-    { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true },
+    { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true },
 };
@@ -227,6 +227,40 @@ int main(int argc, char** argv)
         }
         std::printf(same ? "IDENTICAL\n" : "DIFFERENT\n");
         return same ? 0 : 2;
+    }
+    if (vm.count("dump-jplace")) {
+        // developer aid (no GPU): the jplace writer on rows from a text file.  --dump-jplace FILE with --input-tree; FILE holds per
+        // query a line `NAME K` and K lines `EDGE COUNT DISTAL PENDANT` (strtod: nan and inf are read as such); --bootstrap N sets
+        // the replicates.  The file goes to stdout.
+        std::ifstream tf(strOr(vm, "input-tree", ""));
+        if (!tf) { std::cerr << "ERROR: Unable to open input tree file: " << strOr(vm, "input-tree", "") << "\n"; return 1; }
+        std::string nwk;
+        std::getline(tf, nwk);
+        std::ifstream rf(vm["dump-jplace"]);
+        if (!rf) { std::cerr << "ERROR: cant open file: " << vm["dump-jplace"] << "\n"; return 1; }
+        std::vector<std::string> qnames;
+        std::vector<std::vector<PlacementRow>> rows;
+        std::string nm;
+        size_t k = 0;
+        while (rf >> nm >> k) {
+            qnames.push_back(nm);
+            rows.emplace_back();
+            for (size_t i = 0; i < k; ++i) {
+                std::string e, c, d, pl;
+                if (!(rf >> e >> c >> d >> pl)) die("ERROR: --dump-jplace: a row has four fields");
+                rows.back().push_back(PlacementRow{ (int32_t)std::stol(e), std::stoll(c), std::strtod(d.c_str(), nullptr), std::strtod(pl.c_str(), nullptr) });
+            }
+        }
+        Tree t(nwk, 0);
+        std::vector<std::string> names(t.m_numLeaves, "");
+        names.insert(names.end(), qnames.begin(), qnames.end());
+        Param params;
+        params.in = "m";
+        params.distanceType = stoiOr(vm, "distance-type", 1);
+        BootstrapOptions bo;
+        bo.replicates = (int64_t)stoiOr(vm, "bootstrap", 0);
+        writeJplace(std::cout, t, names, rows, params, bo);
+        return 0;
     }
     if (vm.count("dump-fasta")) {
         // developer aid (no GPU): read --input-file and print name, length and FNV-1a of every record
@@ -488,6 +522,15 @@ int main(int argc, char** argv)
             std::vector<std::vector<PlacementRow>> rows;
             kplacementDeviceArrays.placeFixed(dev, params, boot, rows);
             if (cliLog()) std::cerr << "  queries placed at " << ms_since(inputStart) << " ms\n";
+            {
+                size_t left_out = 0;
+                std::string some;
+                for (size_t q = 0; q < rows.size(); ++q)
+                    if (rows[q].empty() && ++left_out <= 5) some += (left_out > 1 ? ", " : "") + names[backboneSize + q];
+                if (left_out && rankInfo().rank == 0)          // every rank holds all rows: one line, from the rank that writes the file
+                    std::cerr << "Queries without a finite placement (not finite distances to the backbone), left out of the file: " << left_out
+                              << " (" << some << (left_out > 5 ? ", ..." : "") << ")\n";
+            }
             writeJplace(*output_, t, names, rows, params, boot);
             if (cliLog()) std::cerr << "  placements written at " << ms_since(inputStart) << " ms\n";
             printRankSummary(dev.ctx);

@@ -1,6 +1,7 @@
 """Helpers of the fixed-backbone placement tests (`-o j`, dpr_place_fixed_*): seeded rooted binary backbones as Newick, the
 importer's adjacency arrays of a backbone, the edge numbering of a jplace tree string, and the bootstrap tally of the
 command restated in Python."""
+import math
 import re
 
 import numpy as np
@@ -8,12 +9,12 @@ import numpy as np
 from tests import _util
 
 
-def random_backbone(rng, m, kind, zero_frac=0.2, prefix="B"):
+def random_backbone(rng, m, kind, zero_frac=0.2, prefix="B", max_len=0.05):
     """Newick of a rooted binary tree with m >= 2 leaves.  kind: caterpillar | balanced | random.  Leaves are named
     prefix + index of appearance (= the importer's tip index); lengths have four decimals (exact as binary32 -> the text
-    the importer reads is what a "%g" of the stored value gives back), zero_frac of them are 0."""
+    the importer reads is what a "%g" of the stored value gives back), drawn from [0.001, max_len], zero_frac of them are 0."""
     def length():
-        return 0.0 if rng.random() < zero_frac else round(float(rng.uniform(0.001, 0.05)), 4)
+        return 0.0 if rng.random() < zero_frac else round(float(rng.uniform(0.001, max_len)), 4)
 
     if kind == "caterpillar":
         tree = 0
@@ -105,13 +106,24 @@ def row_of(state, slot, frac, add):
     return s >> 1, (float(state["len"][s]) - float(frac)) if s & 1 else float(frac), float(add)
 
 
+def finite_row(row):
+    """a placement the command records: both lengths finite (a pendant length of +inf comes with a NaN position)"""
+    return row is not None and math.isfinite(row[1]) and math.isfinite(row[2])
+
+
 def tally(main, reps):
     """rows of one query as the command lists them: main = (edge, distal, pendant) from the uploaded alignment, reps = the
     same per replicate, in order.  Returns [(edge, count, distal, pendant)]: edges with count > 0 plus the main edge, by count
     descending, the main edge first, then edge ascending; lengths of the main placement for the main edge, else of the
-    lowest-numbered replicate that chose the edge."""
+    lowest-numbered replicate that chose the edge.  A placement whose lengths are not finite is not recorded: no rows at all
+    (the query is left out of the file) when it is the main one, no count for this query when it is a replicate's -- the
+    counts of the query then sum to less than the number of replicates."""
+    if not finite_row(main):
+        return []
     rows = {main[0]: [0, main[1], main[2]]}
     for edge, distal, pendant in reps:
+        if not finite_row((edge, distal, pendant)):
+            continue
         if edge not in rows:
             rows[edge] = [0, distal, pendant]
         rows[edge][0] += 1

@@ -155,3 +155,94 @@ def test_no_output_file_after_a_usage_error(tmp_path):
     out = tmp_path / "u.jplace"
     r = run(*case.args, "--bootstrap", "5", "--bootstrap-metric", "tbe", "-O", str(out))
     assert r.returncode == 1 and "\033[31m" in r.stderr and not out.exists()
+
+
+# ---- queries without a finite placement (left out of the file, which stays JSON) -----------------------------------
+def _no_constant(name):
+    raise AssertionError("not JSON: the bare token %s" % name)
+
+
+class SaturatedCase:
+    """the 40-tip saturated input of tests/test_gpu_place_fixed_edges.py on disk: query 0 is at +inf from every backbone tip (no
+    finite placement), 63 and 64 at NaN (add = 0 on the lowest slot: finite), 129 at +inf from one clade only"""
+
+    def __init__(self, tmp, orc):
+        from tests import test_gpu_place_fixed_edges as E
+        self.m = 40
+        self.inp = E.saturated_input(orc, self.m, "plain")
+        self.nwk = E.backbone(self.m, "random")
+        self.n = len(self.inp.seqs)
+        self.names = ["B%d" % k for k in range(self.m)] + ["Q%d" % k for k in range(self.n - self.m)]
+        self.fasta, self.tree = tmp / "sat.fa", tmp / "sat.nwk"
+        _util.write_fasta(self.fasta, self.names, self.inp.seqs, width=70)
+        self.tree.write_text(self.nwk + "\n")
+        self.args = ["-i", "m", "-I", str(self.fasta), "--add", "-t", str(self.tree), "-o", "j", "-d", "2"]
+
+    def abi_rows(self, orc, replicates, seed):
+        import dipper_amd
+        from dipper_amd import capi
+        d = dipper_amd.Dipper(0)
+        try:
+            d.set_msa(capi.pack4_many(self.inp.seqs), SITES_SAT)
+            self.state, self.leaf_names = _jplace.backbone_arrays(orc, self.nwk, self.n)
+            d.place_fixed_set(self.m, self.n, self.state)
+            place = lambda: [_jplace.row_of(self.state, s, f, a) for s, f, a in zip(*d.place_fixed_run(capi.SRC_MSA, 2))]
+            main, reps = place(), []
+            for rep in range(replicates):
+                d.msa_resample(seed, rep)
+                reps.append(place())
+        finally:
+            d.close()
+        return main, reps
+
+
+SITES_SAT = 200
+# Query 63 differs from every backbone tip in columns [40, 200) and nowhere else: p = 160/200 in the uploaded alignment (NaN under
+# JC: add = 0, placed).  In a replicate that draws those columns exactly 150 times it is at p = 0.75, +inf, from everybody and
+# has no finite placement there.  Replicate 0 of this seed is such a one (found on the host: dpr_msa_boot_weights), 1 and 2 are not.
+BOOT_SEED, SATURATING_REPLICATE = 16, 0
+
+
+@pytest.mark.parametrize("replicates", [0, 3])
+def test_queries_without_a_finite_placement_are_left_out(tmp_path, orc, replicates):
+    from dipper_amd import capi
+    case = SaturatedCase(tmp_path, orc)
+    extra = ["--bootstrap", str(replicates), "--bootstrap-seed", str(BOOT_SEED)] if replicates else []
+    out, out2 = tmp_path / "s.jplace", tmp_path / "s2.jplace"
+    r = run(*case.args, *extra, "-O", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    doc = json.loads(out.read_text(), parse_constant=_no_constant)
+    main, reps = case.abi_rows(orc, replicates, BOOT_SEED)
+    assert not _jplace.finite_row(main[0]) and main[0][2] == float("inf")           # the regime, from the ABI's own triples
+    assert all(_jplace.finite_row(main[q]) and main[q][2] == 0.0 for q in (63, 64))
+    differing = [int(capi.msa_boot_weights(BOOT_SEED, rep, SITES_SAT)[40:].sum()) for rep in range(3)]
+    assert [k == 150 for k in differing] == [rep == SATURATING_REPLICATE for rep in range(3)], differing
+    if replicates:                                        # ... and from the replicates': query 63 is at +inf there, and only there
+        assert [_jplace.finite_row(rep[63]) for rep in reps] == [rep != SATURATING_REPLICATE for rep in range(3)]
+        assert reps[SATURATING_REPLICATE][63][2] == float("inf")
+    want = {case.names[case.m + q]: _jplace.tally(main[q], [rep[q] for rep in reps]) for q in range(len(main))}
+    placed = [nm for nm in case.names[case.m:] if want[nm]]
+    assert "Q0" not in placed and len(placed) < len(main)
+    assert [p["n"] for p in doc["placements"]] == [[nm] for nm in placed]
+    _, below, _, _ = _jplace.jplace_edges(doc["tree"])
+    short = 0
+    for p in doc["placements"]:
+        rows = want[p["n"][0]]
+        if not replicates:
+            rows = [(e, 1, dl, pl) for e, _, dl, pl in rows]
+        assert len(p["p"]) == len(rows)
+        for (e, lik, lwr, dl, pl), (edge, count, distal, pendant) in zip(p["p"], rows):
+            assert below[e] == _jplace.leaves_below_slot(case.state, 2 * edge, case.leaf_names)
+            assert lik == 0 and float(lwr) == count / max(replicates, 1) and float(dl) == distal and float(pl) == pendant
+        short += sum(row[1] for row in rows) < replicates
+    left_out = len(main) - len(placed)
+    lines = [ln for ln in r.stderr.splitlines() if "without a finite placement" in ln]
+    assert len(lines) == 1 and (": %d (" % left_out) in lines[0] and "Q0" in lines[0], r.stderr[-1500:]
+    if replicates:
+        assert short > 0                                  # some replicate's placement of a placed query is not finite: its ratios sum to < 1
+        q63 = next(p for p in doc["placements"] if p["n"] == ["Q63"])
+        assert sum(round(row[2] * replicates) for row in q63["p"]) == replicates - 1
+    r2 = run(*case.args, *extra, "-O", str(out2), "--devices", "0,0")
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    assert out.read_bytes() == out2.read_bytes()
+    assert "Starting 2 ranks" in r2.stderr and [ln for ln in r2.stderr.splitlines() if "without a finite placement" in ln] == lines   # once, not per rank

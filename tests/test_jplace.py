@@ -1,6 +1,7 @@
 """CPU tests of the jplace output (`dipper --add -t ... -o j`): the help text, the usage errors that the arguments alone decide
 (no input read, no GPU touched, no output file), the refusals that keep their wording, and the test helpers of tests/_jplace.py
 (backbone generator, importer arrays, edge numbering of a jplace tree string, the bootstrap tally)."""
+import json
 import os
 import subprocess
 
@@ -131,3 +132,49 @@ def test_tally_orders_rows():
     # the main edge is listed even when no replicate chose it, after the edges with a count
     assert _jplace.tally(main, [(7, 0.1, 0.2)]) == [(7, 1, 0.1, 0.2), (4, 0, 0.5, 0.25)]
     assert _jplace.tally(main, []) == [(4, 0, 0.5, 0.25)]
+
+
+def test_tally_leaves_out_placements_that_are_not_finite():
+    inf, nan = float("inf"), float("nan")
+    main = (4, 0.5, 0.25)
+    assert _jplace.tally((4, nan, inf), [(7, 0.1, 0.2)]) == []                 # no main placement: no record, whatever the replicates say
+    assert _jplace.tally(main, [(7, 0.1, 0.2), (0, nan, inf), (7, 0.3, 0.4)]) == [(7, 2, 0.1, 0.2), (4, 0, 0.5, 0.25)]
+    assert _jplace.tally(main, [(0, nan, inf)] * 3) == [(4, 0, 0.5, 0.25)]
+    assert _jplace.tally((0, 0.01, 0.0), []) == [(0, 0, 0.01, 0.0)]             # add = 0 on the lowest slot (NaN to everything) is finite
+
+
+# ---- the writer (no GPU: --dump-jplace hands rows from a text file to writeJplace) -------------------------------------------------
+TREE = "((a:0.1,b:0):0.25,(c:1e-05,(d:2,e:3):4):5);"
+
+
+def _no_constant(name):
+    raise AssertionError("not JSON: the bare token %s" % name)
+
+
+def _write(tmp_path, binary, rows_text, *extra):
+    (tmp_path / "t.nwk").write_text(TREE + "\n")
+    (tmp_path / "rows.txt").write_text(rows_text)
+    return run(binary, "-t", str(tmp_path / "t.nwk"), "--dump-jplace", str(tmp_path / "rows.txt"), *extra)
+
+
+@pytest.mark.parametrize("sanitized", [False, True])
+def test_writer_writes_finite_rows_and_skips_queries_without_rows(tmp_path, asan_bin, sanitized):
+    r = _write(tmp_path, asan_bin if sanitized else BIN, "q0 1\n3 1 0.25 1e-300\nq1 0\nq2 2\n0 2 0 0.5\n7 1 1.7976931348623157e308 4.9406564584124654e-324\n",
+               "--bootstrap", "3")
+    assert r.returncode == 0, r.stderr
+    doc = json.loads(r.stdout, parse_constant=_no_constant)
+    assert [p["n"] for p in doc["placements"]] == [["q0"], ["q2"]]              # q1 has no rows: no record, and no stray comma
+    assert doc["placements"][0]["p"] == [[3, 0, 1 / 3, 0.25, 1e-300]]
+    assert doc["placements"][1]["p"] == [[0, 0, 2 / 3, 0.0, 0.5], [7, 0, 1 / 3, 1.7976931348623157e308, 5e-324]]
+    only_empty = _write(tmp_path, BIN, "q0 0\nq1 0\n")
+    assert only_empty.returncode == 0 and json.loads(only_empty.stdout, parse_constant=_no_constant)["placements"] == []
+
+
+@pytest.mark.parametrize("sanitized", [False, True])
+@pytest.mark.parametrize("distal,pendant", [("nan", "inf"), ("0.1", "inf"), ("nan", "0.1"), ("0.1", "-inf"), ("inf", "0.1"), ("0.1", "nan")])
+def test_writer_refuses_nan_and_inf(tmp_path, asan_bin, sanitized, distal, pendant):
+    """the writer is handed finite rows only (placeFixed); given anything else it writes nothing and fails, it never emits the
+    tokens nan / inf"""
+    r = _write(tmp_path, asan_bin if sanitized else BIN, "q0 1\n3 1 0.25 0.5\nq1 1\n2 1 %s %s\n" % (distal, pendant))
+    assert r.returncode == 1 and "not finite" in r.stderr, r.stderr
+    assert r.stdout == ""
