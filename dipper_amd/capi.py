@@ -11,6 +11,7 @@ _LIB = None
 
 SRC_MSA, SRC_MASH, SRC_MATRIX = 1, 2, 3
 DIST_UNCORRECTED, DIST_JC = 1, 2
+DIST_POISSON, DIST_KIMURA = 7, 8     # protein alignments only (Dipper.set_msa_aa)
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -42,6 +43,7 @@ def load_library():
     L.dpr_abi_version.restype = C.c_int
     L.dpr_pack4.argtypes = [C.c_char_p, C.c_uint64, c_u64p]
     L.dpr_pack2.argtypes = [C.c_char_p, C.c_uint64, c_u64p]
+    L.dpr_pack_aa.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint8)]
     L.dpr_njr_owner.argtypes = [C.c_int64, C.c_int]
     L.dpr_njr_local_row.argtypes = [C.c_int64, C.c_int]
     L.dpr_njr_local_row.restype = C.c_int64
@@ -102,6 +104,7 @@ def load_library():
     L.dpr_get_njp_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dpr_bw_probe.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.dpr_set_msa.argtypes = [C.c_void_p, c_u64p, C.c_int64, C.c_int64]
+    L.dpr_set_msa_aa.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int64, C.c_int64]
     L.dpr_set_reads.argtypes = [C.c_void_p, c_u64p, c_u64p, c_u64p, C.c_int64]
     L.dpr_set_matrix_lower.argtypes = [C.c_void_p, c_f64p, C.c_int64]
     L.dpr_sketch.argtypes = [C.c_void_p, C.c_int, C.c_int, c_u64p]
@@ -243,6 +246,24 @@ def pack2(seq: bytes):
     L = load_library()
     out = np.zeros((len(seq) + 31) // 32, dtype=np.uint64)
     _chk(L, L.dpr_pack2(seq, len(seq), _p(out, c_u64p)))
+    return out
+
+
+def pack_aa(seq: bytes):
+    """one byte per site: ARNDCQEGHILKMFPSTWYV (either case) -> 0..19, everything else 255 (not a residue)"""
+    L = load_library()
+    out = np.zeros(len(seq), dtype=np.uint8)
+    _chk(L, L.dpr_pack_aa(seq, len(seq), _p(out, C.POINTER(C.c_uint8))))
+    return out
+
+
+def pack_aa_many(seqs):
+    """[n][L] codes, L = len(seqs[0]); a shorter sequence is padded with not-a-residue, a longer one cut"""
+    Ls = len(seqs[0])
+    out = np.full((len(seqs), Ls), 255, dtype=np.uint8)
+    for i, s in enumerate(seqs):
+        c = pack_aa(s)
+        out[i, : min(Ls, len(c))] = c[:Ls]
     return out
 
 
@@ -422,6 +443,12 @@ class Dipper:
     def set_msa(self, packed4, L):
         p = np.ascontiguousarray(packed4, dtype=np.uint64)
         _chk(self.L, self.L.dpr_set_msa(self.h, _p(p, c_u64p), p.shape[0], L))
+
+    def set_msa_aa(self, codes):
+        """protein alignment: codes [n][L] uint8 as pack_aa_many builds them (>= 20: not a residue); source stays SRC_MSA"""
+        p = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert p.ndim == 2
+        _chk(self.L, self.L.dpr_set_msa_aa(self.h, _p(p, C.POINTER(C.c_uint8)), p.shape[0], p.shape[1]))
 
     def set_matrix_lower(self, rows, n):
         r = np.ascontiguousarray(rows, dtype=np.float64)

@@ -167,6 +167,7 @@ int dpr_msa_resample(dpr_ctx* c, uint64_t seed, int64_t replicate)
 {
     if (!c || replicate < -1) { set_error("dpr_msa_resample: bad argument"); return DPR_ERR_ARG; }
     if (!c->msa.planes) { set_error("dpr_msa_resample: call dpr_set_msa first"); return DPR_ERR_STATE; }
+    if (c->msa.aa) { set_error("dpr_msa_resample: bootstrap replicates are not available for a protein alignment (nucleotide alignments only)"); return DPR_ERR_ARG; }
     if (c->msa.L >= ((int64_t)1 << 31)) { set_error("dpr_msa_resample: at most 2^31 - 1 sites"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
     const int rc = msa_resample(c->msa, seed, replicate, c->stream);

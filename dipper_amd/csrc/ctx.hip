@@ -78,6 +78,18 @@ int dpr_pack2(const char* seq, uint64_t len, uint64_t* out)
     return DPR_OK;
 }
 
+// amino acids: ARNDCQEGHILKMFPSTWYV -> 0..19 in either case, everything else 255
+int dpr_pack_aa(const char* seq, uint64_t len, uint8_t* out)
+{
+    if ((!seq || !out) && len) { set_error("dpr_pack_aa: null argument"); return DPR_ERR_ARG; }
+    static const char kLetters[] = "ARNDCQEGHILKMFPSTWYV";
+    uint8_t table[256];
+    for (int i = 0; i < 256; ++i) table[i] = 255;
+    for (int i = 0; i < 20; ++i) { table[(unsigned char)kLetters[i]] = (uint8_t)i; table[(unsigned char)(kLetters[i] + 32)] = (uint8_t)i; }
+    for (uint64_t j = 0; j < len; ++j) out[j] = table[(unsigned char)seq[j]];
+    return DPR_OK;
+}
+
 // ---- sharding helpers -------------------------------------------------------------------------------
 int dpr_njr_owner(int64_t position, int world) { return world > 0 && position >= 0 ? njr_owner(position, world) : -1; }
 int64_t dpr_njr_local_row(int64_t position, int world) { return world > 0 && position >= 0 ? njr_local_row(position, world) : -1; }
@@ -212,6 +224,15 @@ int dpr_set_msa(dpr_ctx* c, const uint64_t* packed4, int64_t n, int64_t L)
     DPR_HIP(hipSetDevice(c->device));
     c->n_input = n;
     return msa_upload(c->msa, packed4, n, L, c->stream);
+}
+
+int dpr_set_msa_aa(dpr_ctx* c, const uint8_t* codes, int64_t n, int64_t L)
+{
+    if (!c || !codes || n < 2 || L < 1) { set_error("dpr_set_msa_aa: bad argument"); return DPR_ERR_ARG; }
+    if (n >= (1 << 24)) { set_error("dpr_set_msa_aa: n must be < 2^24"); return DPR_ERR_ARG; }
+    DPR_HIP(hipSetDevice(c->device));
+    c->n_input = n;
+    return msa_aa_upload(c->msa, codes, n, L, c->stream);
 }
 
 int dpr_set_reads(dpr_ctx* c, const uint64_t* packed2, const uint64_t* word_off, const uint64_t* len, int64_t n)

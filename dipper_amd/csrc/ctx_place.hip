@@ -457,6 +457,7 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
         return DPR_ERR_ARG;
     }
     if (int rc = check_source(c, "dpr_dc_run", source, k, n)) return rc;
+    if (source == DPR_SRC_MSA && c->msa.aa) { set_error("dpr_dc_run: divide-and-conquer is not available for a protein alignment (nucleotide alignments only)"); return DPR_ERR_ARG; }
     const int64_t B = backbone;
     if (int rc = rebuild_place(c, n, B)) return rc;
     PlaceBuffers& p = c->place;

@@ -594,8 +594,8 @@ int dc_cluster_phase(PlaceBuffers& p, const int32_t* h_cluster_id, int64_t N, in
     DPR_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), s));
     DPR_HIP(hipMemcpyAsync(d_members, members.data(), sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, s));
 
-    const int tr_rows = source == DPR_SRC_MSA ? msa_dist_tile_edge(dist_type) : mash_jobs_rows();
-    const int tr_cols = source == DPR_SRC_MSA ? msa_dist_tile_edge(dist_type) : mash_jobs_cols();
+    const int tr_rows = source == DPR_SRC_MSA ? msa_dist_tile_edge(*msa, dist_type) : mash_jobs_rows();
+    const int tr_cols = source == DPR_SRC_MSA ? msa_dist_tile_edge(*msa, dist_type) : mash_jobs_cols();
     std::vector<int64_t> h_moff, h_coff, h_out;
     std::vector<int32_t> h_m, h_ld;
     std::vector<int4> jobs;

@@ -402,6 +402,10 @@ struct MsaBuffers {
     uint32_t* boot_incl = nullptr;  // [L] inclusive scan of boot_w
     int32_t* boot_src = nullptr;    // [32 W32] source column of every replicate position, -1 = padding
     int64_t replicate = -1;         // active replicate, -1 = the uploaded alignment
+    // protein alignment (msa_aa.hip): planes is then [6][n][W32] -- X (not a residue), then the five bits of code + 1, all 0 where
+    // X -- xstage as above, aa_nx[n] the not-a-residue positions of every sequence among its 32 W32; no jc_tab, no replicates
+    bool aa = false;
+    int32_t* aa_nx = nullptr;
 };
 constexpr int64_t kMsaTabSites = 1024;
 constexpr int kMsaBand = 15;
@@ -411,7 +415,7 @@ int msa_restage(MsaBuffers& m, hipStream_t s);     // m.xstage of the active pla
 // mash_index.hip: out[i] = in[0] + ... + in[i] (in and out must not alias); synchronises s
 int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s);
 int msa_dist_rows(const MsaBuffers& m, NjBuffers& b, int dist_type, hipStream_t s);
-int msa_dist_tile_edge(int dist_type);   // rows/columns per job tile of msa_dist_jobs
+int msa_dist_tile_edge(const MsaBuffers& m, int dist_type);   // rows/columns per job tile of msa_dist_jobs
 int msa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s);
 
 // ---- transfer bootstrap expectation (tbe.hip) ----------------------------------------------------------------------------
@@ -494,6 +498,30 @@ int mash_jobs_rows();   // members per job
 int mash_jobs_cols();   // leaf-list positions per job
 int mash_hash_positions(const MashBuffers& m, int64_t seq, int k, uint64_t* d_out, uint64_t len, uint64_t word_off,
                         hipStream_t s);
+
+// What a block of the pair kernels computes: up to PT row sequences x PT column sequences (ids in LDS, -1 = none) and
+// where the PT x PT tile of distances goes.
+constexpr int64_t kNoDiag = (int64_t)1 << 40;
+struct MsaSparseX { const unsigned long long* stage; };
+struct TileOut {
+    double* out;        // element (r, c) of the tile -> out[r * ld + c]            (row-major target)
+    int64_t ld;
+    int nr, nc;         // valid rows / columns of the tile
+    int lower_base;     // >= 0: keep only c_pos < lower_base + r_pos (tile-local positions + tile origins below)
+    int r_org, c_org;   // positions of the tile origin inside its job (for lower_base)
+    double* mir;        // != nullptr: also element (r, c) -> mir[c * mir_ld + r]  (mirror / transposed target)
+    int64_t mir_ld;
+    bool skip_main;     // only the transposed target is written
+    int64_t diag;       // element (r, c) with r + diag == c is a tip against itself -> 0 (kNoDiag: none)
+    const double* tab;  // types 1-2: distance by (useful, match): tab_ld > 0 the full table of a short alignment (row stride tab_ld),
+    int tab_ld;         // tab_ld < 0 the band useful >= L - kMsaBand of a long one (L = -tab_ld - 1); nullptr: computed
+    const unsigned long long* xstage;   // types 1-2: per sequence, the stages that hold a not-a-base position (nullptr: every stage of every sequence)
+};
+// msa_aa.hip: the protein alphabet behind the same entry points (msa.hip dispatches on MsaBuffers::aa)
+int msa_aa_upload(MsaBuffers& m, const uint8_t* codes, int64_t n, int64_t L, hipStream_t s);
+int msa_aa_launch(int dist_type, hipStream_t s, const MsaBuffers& m, double* D, int64_t ld, int64_t rows, int rank, int world,
+                  int64_t row0, int64_t col0, int64_t ncols, int transposed);
+int msa_aa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s);
 
 // msa.hip: same row-provider shape as mash_dist_rows
 // transposed: out[j * ld + t] instead of out[t * ld + j]

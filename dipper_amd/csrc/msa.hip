@@ -210,25 +210,6 @@ __global__ __launch_bounds__(kThreads) void msa_jc_table_kernel(int L, double* _
 template <int TYPE> struct TileOf { static constexpr int SUB = 2; };              // 32 x 32 pairs, 2 x 2 per thread
 template <> struct TileOf<DPR_DIST_JC> { static constexpr int SUB = 4; };         // 64 x 64 pairs, 4 x 4 per thread
 
-// What a block computes: up to PT row sequences x PT column sequences (ids in LDS, -1 = none) and
-// where the PT x PT tile of distances goes.
-constexpr int64_t kNoDiag = (int64_t)1 << 40;
-struct MsaSparseX { const unsigned long long* stage; };
-struct TileOut {
-    double* out;        // element (r, c) of the tile -> out[r * ld + c]            (row-major target)
-    int64_t ld;
-    int nr, nc;         // valid rows / columns of the tile
-    int lower_base;     // >= 0: keep only c_pos < lower_base + r_pos (tile-local positions + tile origins below)
-    int r_org, c_org;   // positions of the tile origin inside its job (for lower_base)
-    double* mir;        // != nullptr: also element (r, c) -> mir[c * mir_ld + r]  (mirror / transposed target)
-    int64_t mir_ld;
-    bool skip_main;     // only the transposed target is written
-    int64_t diag;       // element (r, c) with r + diag == c is a tip against itself -> 0 (kNoDiag: none)
-    const double* tab;  // types 1-2: distance by (useful, match): tab_ld > 0 the full table of a short alignment (row stride tab_ld),
-    int tab_ld;         // tab_ld < 0 the band useful >= L - kMsaBand of a long one (L = -tab_ld - 1); nullptr: computed
-    const unsigned long long* xstage;   // types 1-2: per sequence, the stages that hold a not-a-base position (nullptr: every stage of every sequence)
-};
-
 // Block of 256 threads = 16 x 16; thread (ty,tx) owns rows ty*SUB.., cols tx*SUB..
 // LDS: [side][plane][k][PT (+4) sequences] so that SUB consecutive sequences are one 16/8-byte read;
 // rows padded by 4 words: the staging writes (consecutive lanes = consecutive k) then hit 8 banks two
@@ -571,6 +552,7 @@ static int launch_matrix(dim3 grid, hipStream_t s, const uint32_t* planes, int64
 static int msa_launch(int dist_type, hipStream_t s, const MsaBuffers& m, double* D, int64_t ld, int64_t rows, int rank,
                       int world, int64_t row0, int64_t col0, int64_t ncols, int transposed)
 {
+    if (m.aa) return msa_aa_launch(dist_type, s, m, D, ld, rows, rank, world, row0, col0, ncols, transposed);
     const int pt = (dist_type == DPR_DIST_UNCORRECTED || dist_type == DPR_DIST_JC) ? 64 : 32;
     dim3 g((unsigned)((ncols + pt - 1) / pt), (unsigned)((rows + pt - 1) / pt));
     switch (dist_type) {
@@ -584,10 +566,11 @@ static int msa_launch(int dist_type, hipStream_t s, const MsaBuffers& m, double*
     }
 }
 
-int msa_dist_tile_edge(int dist_type) { return (dist_type == DPR_DIST_UNCORRECTED || dist_type == DPR_DIST_JC) ? 64 : 32; }
+int msa_dist_tile_edge(const MsaBuffers& m, int dist_type) { return (m.aa || dist_type == DPR_DIST_UNCORRECTED || dist_type == DPR_DIST_JC) ? 64 : 32; }
 
 int msa_dist_jobs(const MsaBuffers& m, int dist_type, const PairJobs& J, int njobs, hipStream_t s)
 {
+    if (m.aa) { set_error("cluster distances (divide-and-conquer) are not available for a protein alignment"); return DPR_ERR_ARG; }
     if (njobs <= 0) return DPR_OK;
     switch (dist_type) {
     case DPR_DIST_UNCORRECTED:
@@ -667,6 +650,7 @@ void msa_free(MsaBuffers& m)
     if (m.boot_w) (void)hipFree(m.boot_w);
     if (m.boot_incl) (void)hipFree(m.boot_incl);
     if (m.boot_src) (void)hipFree(m.boot_src);
+    if (m.aa_nx) (void)hipFree(m.aa_nx);
     m = MsaBuffers();
 }
 
@@ -695,6 +679,7 @@ int msa_dist_block_rows(const MsaBuffers& m, int64_t r0, int64_t nr, int rank, i
 int msa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s)
 {
     if (row <= 0) return DPR_OK;
+    if (m.aa) return msa_aa_counts_row(m, row, d_useful, d_match, s);
     const unsigned grid = (unsigned)((row + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(msa_counts_row_kernel, dim3(grid), dim3(kThreads), 0, s, m.planes, m.n, m.W32, row,
                        d_useful, d_match);

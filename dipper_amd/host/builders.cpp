@@ -145,6 +145,27 @@ void MSADeviceArrays::allocateDeviceArrays(DeviceContext& dev, const std::vector
     gpuCheck(dpr_set_msa(dev.ctx, flat.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa");
 }
 
+void MSADeviceArrays::allocateDeviceArraysProtein(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids)
+{
+    numSequences = seqs.size();
+    if (numSequences < 2) die("ERROR: need at least two sequences");
+    size_t slot0 = 0;
+    for (size_t i = 0; i < numSequences; ++i) if (ids[i] == 0) slot0 = i;
+    seqLen = (int)seqs[slot0].size();
+    if (seqLen < 1) die("ERROR: the first sequence of the alignment is empty");
+    const size_t L = (size_t)seqLen;
+    std::vector<uint8_t> codes(numSequences * L, (uint8_t)255);
+    const unsigned nt = hostThreads(32);
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nt; ++t)
+        pool.emplace_back([&, t] {
+            for (size_t i = t; i < numSequences; i += nt)
+                dpr_pack_aa(seqs[i].data(), std::min(seqs[i].size(), L), codes.data() + (size_t)ids[i] * L);
+        });
+    for (auto& th : pool) th.join();
+    gpuCheck(dpr_set_msa_aa(dev.ctx, codes.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa_aa");
+}
+
 void NJDeviceArrays::getDismatrix(DeviceContext& dev, int numSequences, Param& params, MatrixReader* matrixReader)
 {
     d_numSequences = numSequences;

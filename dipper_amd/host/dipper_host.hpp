@@ -28,6 +28,7 @@ struct Param {  // src/mash_placement.cuh:16-32
     uint64_t kmerSize = 15, sketchSize = 1000, threshold = 1, distanceType = 1;
     std::string in = "r", out = "t";
     uint64_t batchSize = 0, backboneSize = 0;
+    bool protein = false;      // --protein: the aligned input holds amino acids (no reference counterpart)
 };
 
 [[noreturn]] void die(const std::string& msg);   // prints msg to stderr, exit(1)
@@ -154,6 +155,9 @@ struct MSADeviceArrays {  // src/mash_placement.cuh:87-98
     // seqs[i] goes to slot ids[i]; packs with the 4-bit encoder in parallel and uploads
     void allocateDeviceArrays(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids);
     void allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed);      // already packed by readSequencesPacked
+    // --protein: seqs[i] goes to slot ids[i], one byte per site (dpr_pack_aa), seqLen = length of the sequence in slot 0; a
+    // shorter sequence ends in not-a-residue positions
+    void allocateDeviceArraysProtein(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids);
 };
 
 struct NJDeviceArrays {  // src/mash_placement.cuh:199-212

@@ -64,8 +64,10 @@ static const char* distanceName(const Param& params)
 {
     if (params.in == "r") return "mash";
     switch (params.distanceType) {
-    case DPR_DIST_UNCORRECTED: return "uncorrected";
-    case DPR_DIST_JC: return "JC";
+    case DPR_DIST_UNCORRECTED: return params.protein ? "protein uncorrected" : "uncorrected";
+    case DPR_DIST_JC: return params.protein ? "protein JC (20 states)" : "JC";
+    case DPR_DIST_POISSON: return "protein Poisson";
+    case DPR_DIST_KIMURA: return "protein Kimura";
     case DPR_DIST_TAJIMANEI: return "Tajima-Nei";
     case DPR_DIST_K2P: return "K2P";
     case DPR_DIST_TAMURA: return "Tamura";

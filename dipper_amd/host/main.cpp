@@ -57,6 +57,8 @@ static const char* kHelp =
     "                                4 - K2P\n"
     "                                5 - Tamura\n"
     "                                6 - Jinnei\n"
+    "                                7 - Poisson correction (--protein only)\n"
+    "                                8 - Kimura 1983 (--protein only)\n"
     "  -a [ --add ]                Add query to backbone using k-closest placement\n"
     "  -t [ --input-tree ] arg     Input backbone tree (Newick format), required with --add option\n"
     "  -h [ --help ]               Print this help message\n\n"
@@ -72,6 +74,11 @@ static const char* kHelp =
     "  --rank arg --world arg --rendezvous arg\n"
     "                              this process is rank `rank` of `world` ranks started from outside;\n"
     "                              they meet in the POSIX shared memory object `rendezvous`\n"
+    "  --protein                   The alignment holds amino acids (-i m only): the 20 letters\n"
+    "                              ARNDCQEGHILKMFPSTWYV in either case, anything else is a gap; distances\n"
+    "                              over the sites where both sequences hold a residue.  -d 1 (p-distance,\n"
+    "                              default), 2 (JC with 20 states), 7 or 8; conventional NJ, placement,\n"
+    "                              --add and -o d / -o j; not with --bootstrap or divide-and-conquer\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -99,7 +106,7 @@ static const Opt kOpts[] = {
     { "seed", 0, true }, { "device", 0, true }, { "gpus", 0, true }, { "devices", 0, true }, { "transport", 0, true },
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
-    { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true },
+    { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
 };
 
 static void usageError(const std::string& what)
@@ -278,6 +285,16 @@ int main(int argc, char** argv)
         if (!vm.count(req)) usageError(std::string("the option '--") + req + "' is required but missing");
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
+    // --protein: what the arguments alone decide, before any input is read or a GPU touched
+    const bool protein = vm.count("protein") != 0;
+    if (protein) {
+        if (strOr(vm, "input-format", "r") != "m") usageError("--protein needs aligned sequences (-i m)");
+        const uint64_t dt = stoiOr(vm, "distance-type", 1);
+        if (dt >= DPR_DIST_TAJIMANEI && dt <= DPR_DIST_JINNEI) usageError("-d 3 to 6 are nucleotide models: --protein takes -d 1, 2, 7 or 8");
+        if (dt != DPR_DIST_UNCORRECTED && dt != DPR_DIST_JC && dt != DPR_DIST_POISSON && dt != DPR_DIST_KIMURA) usageError("--protein takes -d 1, 2, 7 or 8");
+        if (vm.count("bootstrap")) usageError("--bootstrap is not available with --protein (nucleotide alignments only)");
+        if (strOr(vm, "algorithm", "0") == "3") usageError("divide-and-conquer (-m 3) is not available with --protein; use -m 1 or -m 2");
+    }
     // -o j (placements on a fixed backbone): what the arguments alone decide, before any input is read or a GPU touched
     const bool jplace = strOr(vm, "output-format", "t") == "j";
     if (jplace) {
@@ -350,6 +367,7 @@ int main(int argc, char** argv)
     params.distanceType = stoiOr(vm, "distance-type", 1);  // code default is 1 although the help says JC
     params.in = strOr(vm, "input-format", "r");
     params.out = strOr(vm, "output-format", "t");
+    params.protein = protein;
     const std::string algo = strOr(vm, "algorithm", "0");
     const std::string placemode = strOr(vm, "placement-mode", "1");  // the reference reads --algorithm here
     const bool add = vm.count("add") != 0;
@@ -483,8 +501,8 @@ int main(int argc, char** argv)
         if (!multi) adev.reset(new AsyncDeviceContext(device));
         const std::function<std::vector<int>(const std::vector<std::string>&)> ids_fn =
             [&](const std::vector<std::string>& nd) { return slots_of(nd, nullptr); };
-        PackedSequences packed;
-        readSequencesPacked(inputFile, params.in == "m", -1, packed, nullptr, nullptr, &ids_fn);
+        PackedSequences packed;      // (--protein: the general reader and the per-sequence encoder, as FASTQ)
+        if (!protein) readSequencesPacked(inputFile, params.in == "m", -1, packed, nullptr, nullptr, &ids_fn);
         std::vector<std::string> seqs, names;
         std::vector<int> ids;
         if (!packed.ok) {                         // FASTQ: serial parser + the per-sequence encoders
@@ -512,6 +530,7 @@ int main(int argc, char** argv)
         } else {
             MSADeviceArrays msaDeviceArrays;
             if (packed.ok) msaDeviceArrays.allocateDeviceArrays(dev, packed);
+            else if (protein) msaDeviceArrays.allocateDeviceArraysProtein(dev, seqs, ids);
             else msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
         }
         if (cliLog()) std::cerr << "  sequences on the device (sketches built) at " << ms_since(inputStart) << " ms\n";
@@ -561,7 +580,8 @@ int main(int argc, char** argv)
         NJDeviceArrays njDeviceArrays;
         if (aligned) {
             MSADeviceArrays msaDeviceArrays;
-            msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
+            if (protein) msaDeviceArrays.allocateDeviceArraysProtein(dev, seqs, ids);
+            else msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
         } else {
             MashDeviceArrays mashDeviceArrays;
             mashDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
@@ -598,8 +618,8 @@ int main(int argc, char** argv)
         // fast path: records indexed in the mapped text and packed straight into the device interface's flat arrays;
         // as soon as the number of records is known the device thread allocates the NJ matrices (when NJ is the mode)
         struct Hook { AsyncDeviceContext* adev; decltype(pick_mode)* pick; } hook{ adev.get(), &pick_mode };
-        PackedSequences packed;
-        readSequencesPacked(inputFile, aligned, seed, packed, [](size_t n, void* u) {
+        PackedSequences packed;      // (--protein: the general reader and the per-sequence encoder, as FASTQ)
+        if (!protein) readSequencesPacked(inputFile, aligned, seed, packed, [](size_t n, void* u) {
             Hook* h = static_cast<Hook*>(u);
             if (h->adev && n >= 3 && (*h->pick)((long long)n) == 2) h->adev->reserveNJ(n);
         }, &hook);
@@ -620,6 +640,9 @@ int main(int argc, char** argv)
         if (boot.replicates > 0 && pick_mode((long long)numSequences) != 2)
             die("ERROR: --bootstrap needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (protein && pick_mode((long long)numSequences) == 3)
+            die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
+                " sequences select it in the default mode; use -m 1 or -m 2");
         if (multi) { startRanks(ranks, device); adev.reset(new AsyncDeviceContext(rankInfo().device)); }
         auto output_ = open_out();
         std::unique_ptr<std::ofstream> taxaOut;
@@ -638,7 +661,8 @@ int main(int argc, char** argv)
             if (aligned) msaDeviceArrays.allocateDeviceArrays(dev, packed);
             else mashDeviceArrays.allocateDeviceArrays(dev, packed);
         } else {
-            if (aligned) msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
+            if (protein) msaDeviceArrays.allocateDeviceArraysProtein(dev, seqs, ids);
+            else if (aligned) msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
             else mashDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
         }
         std::cerr << "Input in: " << ms_since(inputStart) << " ms\n";

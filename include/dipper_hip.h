@@ -45,6 +45,12 @@ extern "C" {
 #define DPR_DIST_K2P 4
 #define DPR_DIST_TAMURA 5
 #define DPR_DIST_JINNEI 6
+/* protein alignments only (dpr_set_msa_aa; no reference counterpart).  With p = 1 - match / useful over the sites where both
+ * sequences hold one of the 20 residues (pairwise deletion), all in fp64 in this operation order:
+ *   1 p   2 -0.95 * log(1.0 - p / 0.95)   7 -log(1.0 - p)   8 -log(1.0 - p - 0.2 * p * p)  (Kimura 1983)
+ * Types 3-6 are nucleotide models (DPR_ERR_ARG on a protein alignment); 7-8 are DPR_ERR_ARG on a nucleotide alignment. */
+#define DPR_DIST_POISSON 7
+#define DPR_DIST_KIMURA 8
 
 /* error codes */
 #define DPR_OK 0
@@ -64,6 +70,9 @@ int dpr_abi_version(void);
  * (src/twoBitCompressor.cpp:5-41): out has ceil(len/16) resp. ceil(len/32) words. */
 int dpr_pack4(const char *seq, uint64_t len, uint64_t *out);
 int dpr_pack2(const char *seq, uint64_t len, uint64_t *out);
+/* amino acids (no reference counterpart): out has len bytes; the 20 letters ARNDCQEGHILKMFPSTWYV, in either case, become
+ * 0..19 in that order, every other byte (gaps, X, B, Z, J, U, O, *, digits, ...) 255 = not a residue. */
+int dpr_pack_aa(const char *seq, uint64_t len, uint8_t *out);
 
 /* ---- host-only sharding helpers (pure functions; used by the N>1 host logic and its CPU tests) */
 /* ... and of the ROW-SHARDED EXACT PRUNED NJ (njr.hip; several ranks, dpr_ctx_set_nj_multi_plan(ctx, 3) / DPR_NJ_MULTI=rows, or
@@ -142,6 +151,11 @@ int dpr_shared_gather(void *shared, int rank, int world, uint32_t *sense, int ti
 /* MSADeviceArrays::allocateDeviceArrays (src/MSA.cu:14-72): packed4 is [n][ceil(L/16)] words as
  * produced by dpr_pack4; L = length of sequence 0 (src/MSA.cu:19). */
 int dpr_set_msa(dpr_ctx *ctx, const uint64_t *packed4, int64_t n, int64_t L);
+/* Protein alignment (no reference counterpart): codes is row-major [n][L], one byte per site as dpr_pack_aa writes it; any
+ * value >= 20 is not a residue.  Argument limits of dpr_set_msa.  The source stays DPR_SRC_MSA: the alphabet belongs to the
+ * uploaded alignment, and each of dpr_set_msa / dpr_set_msa_aa replaces whatever alignment the context held.  Distance types
+ * 1, 2, 7, 8 (above).  dpr_msa_resample and dpr_dc_run refuse a protein alignment (DPR_ERR_ARG). */
+int dpr_set_msa_aa(dpr_ctx *ctx, const uint8_t *codes, int64_t n, int64_t L);
 /* MashDeviceArrays::allocateDeviceArrays (src/mash.cu:14-122): packed2 flat, word_off[i] = first
  * word of sequence i (exclusive scan of ceil(len/32), src/mash.cu:109-119), len[i] in bases. */
 int dpr_set_reads(dpr_ctx *ctx, const uint64_t *packed2, const uint64_t *word_off,
