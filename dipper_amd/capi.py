@@ -12,6 +12,7 @@ _LIB = None
 SRC_MSA, SRC_MASH, SRC_MATRIX = 1, 2, 3
 DIST_UNCORRECTED, DIST_JC = 1, 2
 DIST_POISSON, DIST_KIMURA = 7, 8     # protein alignments only (Dipper.set_msa_aa)
+DIST_TN93, DIST_LOGDET, DIST_PARALINEAR = 9, 10, 11     # nucleotide alignments only (Dipper.set_msa)
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)

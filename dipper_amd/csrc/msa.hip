@@ -175,6 +175,91 @@ struct PairCounts<DPR_DIST_JC> {
         return (g >= 0 && g <= kMsaBand) ? tab[(int64_t)g * (L + 1) + (sites - mism)] : value(dist_type);
     }
 };
+// ------------------------------------------------------------------------------------------------
+// Types 9-11 (TN93, LogDet, paralinear; definitions in include/dipper_hip.h; no reference counterpart): the full table
+// F[row base][column base] over the sites valid in both sequences.  Per 32 bases of a (row r, column c) pair, with the one-hot
+// masks of each side (A = V & ~(HI | LO), C = LO & ~HI, G = HI & ~LO, T = HI & LO: LO and HI are 0 where the site is not a base,
+// so a row mask ANDed with a column mask is already restricted to the sites valid in both)
+//   F[i][j] += popc(R_i & C_j)                      16 and + 16 accumulating popcounts
+// The masks depend on one side only: the 2 x 2 pairs of a thread share them (four masks per sequence and word).
+// One instantiation (TYPE = DPR_DIST_TN93) serves the three types; the epilogue is picked at run time.
+// Epilogues: every input is an integer that does not change when row and column swap -- a_i = r_i + c_i, F[i][j] + F[j][i],
+// N, the trace, r_i c_i, and det F, which is exact (2 x 2 minors of rows (0,1) and (2,3) in int64, their six products summed
+// in __int128) -- so D[a][b] and D[b][a] are the same bits wherever they are computed, and the NaN / +inf pattern is exact.
+// TN93's three log arguments are formed as exact integer fractions too (a saturated pair is as accurate as any other):
+//   1 - P1/k1 - Q/(2gR)  = (aA aG aR - S1 aR^2 - V aA aG) / (aA aG aR)      S1 = F[A][G] + F[G][A], V = transversions (count)
+//   1 - P2/k2 - Q/(2gY)  = (aC aT aY - S2 aY^2 - V aC aT) / (aC aT aY)      S2 = F[C][T] + F[T][C]
+//   1 - Q/(2 gR gY)      = (aR aY - 2 N V) / (aR aY)
+// (a_i <= 2N < 2^32, so aA aG <= N^2 fits int64 and every numerator fits __int128).
+// ------------------------------------------------------------------------------------------------
+// correctly rounded __int128 -> double (the compiler's conversion is a library call the device does not have)
+__device__ __forceinline__ double i128_to_double(__int128 v)
+{
+    const bool neg = v < 0;
+    const unsigned __int128 m = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
+    double d;
+    if (hi == 0) d = (double)lo;
+    else {
+        const int sh = 64 - __clzll((long long)hi);       // 1..64: the top 64 bits, the bits below kept as a sticky bit
+        const uint64_t top = (uint64_t)(m >> sh), rest = sh == 64 ? lo : (lo & ((1ull << sh) - 1ull));
+        d = ldexp((double)(top | (rest ? 1ull : 0ull)), sh);
+    }
+    return neg ? -d : d;
+}
+
+template <>
+struct PairCounts<DPR_DIST_TN93> {
+    int F[4][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
+    // valid planes V = ~X of both sides
+    __device__ __forceinline__ void add(uint32_t vr, uint32_t lr, uint32_t hr, uint32_t vc, uint32_t lc, uint32_t hc)
+    {
+        const uint32_t R[4] = { vr & ~(hr | lr), lr & ~hr, hr & ~lr, hr & lr };
+        const uint32_t C[4] = { vc & ~(hc | lc), lc & ~hc, hc & ~lc, hc & lc };
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) F[i][j] += __popc(R[i] & C[j]);
+    }
+    __device__ __forceinline__ __int128 det() const
+    {
+        // Laplace expansion over the complementary 2 x 2 minors of rows (0,1) and rows (2,3)
+        auto m2 = [&](int r, int j, int k) { return (int64_t)F[r][j] * F[r + 1][k] - (int64_t)F[r][k] * F[r + 1][j]; };
+        return (__int128)m2(0, 0, 1) * m2(2, 2, 3) - (__int128)m2(0, 0, 2) * m2(2, 1, 3) + (__int128)m2(0, 0, 3) * m2(2, 1, 2)
+             + (__int128)m2(0, 1, 2) * m2(2, 0, 3) - (__int128)m2(0, 1, 3) * m2(2, 0, 2) + (__int128)m2(0, 2, 3) * m2(2, 0, 1);
+    }
+    __device__ __forceinline__ double value(int dist_type) const
+    {
+        int64_t r[4], c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            r[i] = (int64_t)F[i][0] + F[i][1] + F[i][2] + F[i][3];
+            c[i] = (int64_t)F[0][i] + F[1][i] + F[2][i] + F[3][i];
+        }
+        const int64_t N = r[0] + r[1] + r[2] + r[3];
+        if (dist_type == DPR_DIST_LOGDET) {
+            const double n = (double)N, n2 = n * n;
+            return -0.25 * log(256.0 * i128_to_double(det()) / (n2 * n2));      // = -1/4 ln(det / N^4) - ln 4
+        }
+        if (dist_type == DPR_DIST_PARALINEAR) {
+            const double prod = (double)(r[0] * c[0]) * (double)(r[1] * c[1]) * (double)(r[2] * c[2]) * (double)(r[3] * c[3]);
+            return -0.25 * log(i128_to_double(det()) / sqrt(prod));
+        }
+        const int64_t aA = r[0] + c[0], aC = r[1] + c[1], aG = r[2] + c[2], aT = r[3] + c[3], aR = aA + aG, aY = aC + aT;
+        const int64_t S1 = (int64_t)F[0][2] + F[2][0], S2 = (int64_t)F[1][3] + F[3][1];
+        const int64_t V = N - ((int64_t)F[0][0] + F[1][1] + F[2][2] + F[3][3]) - S1 - S2;
+        const int64_t pAG = aA * aG, pCT = aC * aT, pRY = aR * aY;
+        const __int128 den1 = (__int128)pAG * aR, den2 = (__int128)pCT * aY;
+        const __int128 num1 = den1 - (__int128)(S1 * aR) * aR - (__int128)V * pAG;
+        const __int128 num2 = den2 - (__int128)(S2 * aY) * aY - (__int128)V * pCT;
+        const __int128 num3 = (__int128)pRY - (__int128)(2 * N) * V;
+        const double n = (double)N, dR = (double)aR, dY = (double)aY, dAG = (double)pAG, dCT = (double)pCT, dRY = (double)pRY;
+        const double k1 = dAG / (n * dR), k2 = dCT / (n * dY);
+        const double k3 = (dRY - dAG * dY / dR - dCT * dR / dY) / (2.0 * n * n);
+        return -k1 * log(i128_to_double(num1) / i128_to_double(den1)) - k2 * log(i128_to_double(num2) / i128_to_double(den2))
+               - k3 * log(i128_to_double(num3) / dRY);
+    }
+};
 // long alignments: the band useful = L - g, g = 0 .. kMsaBand, of that table: tab[type][g][match]
 __global__ __launch_bounds__(kThreads) void msa_jc_band_kernel(int L, double* __restrict__ tab)
 {
@@ -207,8 +292,13 @@ __global__ __launch_bounds__(kThreads) void msa_jc_table_kernel(int L, double* _
     tab[ld * ld + i] = msa_epilogue(useful, match, DPR_DIST_JC);
 }
 
-template <int TYPE> struct TileOf { static constexpr int SUB = 2; };              // 32 x 32 pairs, 2 x 2 per thread
-template <> struct TileOf<DPR_DIST_JC> { static constexpr int SUB = 4; };         // 64 x 64 pairs, 4 x 4 per thread
+// SUB x SUB pairs per thread (tile edge 16 SUB) and the waves per SIMD the front-ends are compiled for
+template <int TYPE> struct TileOf { static constexpr int SUB = 2, WAVES = MSA_WAVES; };        // 32 x 32 pairs
+template <> struct TileOf<DPR_DIST_JC> { static constexpr int SUB = 4, WAVES = MSA_WAVES; };   // 64 x 64 pairs
+// types 9-11: 64 counters per thread.  Under the 128 registers of MSA_WAVES = 4 the compiler spills more than 400 registers (loads
+// and stores between the popcounts of the inner loop; 100 with an empty epilogue), under the 168 of 3 waves still 45; compiled for
+// 2 waves the front-ends take 196 and 190 registers and no scratch.  (Own tile below: msa_tile<DPR_DIST_TN93>.)
+template <> struct TileOf<DPR_DIST_TN93> { static constexpr int SUB = 2, WAVES = 2; };
 
 // Block of 256 threads = 16 x 16; thread (ty,tx) owns rows ty*SUB.., cols tx*SUB..
 // LDS: [side][plane][k][PT (+4) sequences] so that SUB consecutive sequences are one 16/8-byte read;
@@ -449,6 +539,83 @@ __device__ __forceinline__ void msa_tile(const uint32_t* __restrict__ planes, in
         }
 }
 
+// Types 9-11: the 32 x 32 tile with the 64 counters of PairCounts<DPR_DIST_TN93> per thread.  Staging as in the types 1-2 tile: a
+// thread owns one sequence of ONE side (threads 0-127 the rows, 128-255 the columns) and one word quad of its three planes -- three
+// 16-byte loads live beside the counters instead of the generic loop's twelve words and their addresses.
+template <>
+__device__ __forceinline__ void msa_tile<DPR_DIST_TN93>(const uint32_t* __restrict__ planes, int64_t n, int64_t W32, int dist_type,
+                                                        const int32_t* s_rid, const int32_t* s_cid, const TileOut& o, char* smem)
+{
+    constexpr int PT = 32, LDP = PT + 4;
+    typedef uint32_t (*Stage)[kKC][LDP];
+    Stage sA = reinterpret_cast<Stage>(smem);
+    Stage sB = reinterpret_cast<Stage>(smem + sizeof(uint32_t) * 3 * kKC * LDP);
+    const int tid = threadIdx.x;
+    const int tx = tid & 15, ty = tid >> 4;
+    PairCounts<DPR_DIST_TN93> acc[2][2];
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+    const int sq = (tid >> 2) & (PT - 1), kq = tid & 3;
+    const bool cols = tid >= 4 * PT;
+    const int64_t g = cols ? s_cid[sq] : s_rid[sq];
+    Stage sS = cols ? sB : sA;
+    for (int64_t k0 = 0; k0 < W32; k0 += kKC) {
+        const int64_t k = k0 + 4 * kq;
+        const bool whole = k + 3 < W32;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            u32x4 v = (u32x4)(p == 0 ? ~0u : 0u);      // padding words and missing sequences = not a base
+            if (whole) {
+                if (g >= 0) v = *reinterpret_cast<const u32x4*>(planes + ((int64_t)p * n + g) * W32 + k);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k + j < W32 && g >= 0) v[j] = planes[((int64_t)p * n + g) * W32 + k + j];
+            }
+            if (p == 0) v = ~v;                        // the valid plane V = ~X
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sS[p][4 * kq + j][sq] = v[j];
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int kk = 0; kk < kKC; ++kk) {
+            const uint2 aV = *reinterpret_cast<const uint2*>(&sA[0][kk][ty * 2]);
+            const uint2 aL = *reinterpret_cast<const uint2*>(&sA[1][kk][ty * 2]);
+            const uint2 aH = *reinterpret_cast<const uint2*>(&sA[2][kk][ty * 2]);
+            const uint2 bV = *reinterpret_cast<const uint2*>(&sB[0][kk][tx * 2]);
+            const uint2 bL = *reinterpret_cast<const uint2*>(&sB[1][kk][tx * 2]);
+            const uint2 bH = *reinterpret_cast<const uint2*>(&sB[2][kk][tx * 2]);
+            acc[0][0].add(aV.x, aL.x, aH.x, bV.x, bL.x, bH.x);
+            acc[0][1].add(aV.x, aL.x, aH.x, bV.y, bL.y, bH.y);
+            acc[1][0].add(aV.y, aL.y, aH.y, bV.x, bL.x, bH.x);
+            acc[1][1].add(aV.y, aL.y, aH.y, bV.y, bL.y, bH.y);
+        }
+        __syncthreads();
+    }
+    // distances into the LDS tile (row stride PT+1 doubles), then coalesced rows in both orientations
+    double* T = reinterpret_cast<double*>(smem);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int rr = ty * 2 + r, cc = tx * 2 + c;
+            double d = 0.0;
+            if (rr < o.nr && cc < o.nc && rr + o.diag != cc) d = acc[r][c].value(dist_type);
+            T[rr * (PT + 1) + cc] = d;
+        }
+    __syncthreads();
+    if (!o.skip_main)
+        for (int e = tid; e < PT * PT; e += kThreads) {
+            const int rr = e / PT, cc = e % PT;
+            if (rr < o.nr && cc < o.nc && (o.lower_base < 0 || o.c_org + cc < o.lower_base + o.r_org + rr))
+                o.out[(int64_t)rr * o.ld + cc] = T[rr * (PT + 1) + cc];
+        }
+    if (o.mir)
+        for (int e = tid; e < PT * PT; e += kThreads) {
+            const int cc = e / PT, rr = e % PT;
+            if (rr < o.nr && cc < o.nc) o.mir[(int64_t)cc * o.mir_ld + rr] = T[rr * (PT + 1) + cc];
+        }
+}
+
 template <int TYPE> constexpr size_t msa_tile_lds()
 {
     constexpr int PT = 16 * TileOf<TYPE>::SUB;
@@ -460,7 +627,7 @@ template <int TYPE> constexpr size_t msa_tile_lds()
 // against columns col0 + [0, ncols).  world == 1: only tiles on or below the diagonal are computed and
 // mirrored (counts are symmetric, src/MSA.cu:121-122).  transposed: out[(c - col0) * ld + l].
 template <int TYPE>
-__global__ __launch_bounds__(kThreads, MSA_WAVES) void msa_dist_kernel(const uint32_t* __restrict__ planes, int64_t n, int64_t W32,
+__global__ __launch_bounds__(kThreads, TileOf<TYPE>::WAVES) void msa_dist_kernel(const uint32_t* __restrict__ planes, int64_t n, int64_t W32,
                                                             int dist_type, double* __restrict__ D, int64_t ld,
                                                             int64_t rows_local, int rank, int world, int64_t row0,
                                                             int64_t col0, int64_t ncols, int transposed, const double* __restrict__ tab, int tab_ld,
@@ -503,7 +670,7 @@ __global__ __launch_bounds__(kThreads, MSA_WAVES) void msa_dist_kernel(const uin
 // rows = the cluster's members, columns = its leaf list (ids, -1 = empty); element (t, u) with
 // u < 10 + t goes to out[cl_out + t * cl_ld + u].
 template <int TYPE>
-__global__ __launch_bounds__(kThreads, MSA_WAVES) void msa_dist_jobs_kernel(const uint32_t* __restrict__ planes, int64_t n,
+__global__ __launch_bounds__(kThreads, TileOf<TYPE>::WAVES) void msa_dist_jobs_kernel(const uint32_t* __restrict__ planes, int64_t n,
                                                                  int64_t W32, int dist_type, PairJobs J, const double* __restrict__ tab, int tab_ld,
                                                                  MsaSparseX xs)
 {
@@ -529,6 +696,8 @@ __global__ __launch_bounds__(kThreads, MSA_WAVES) void msa_dist_jobs_kernel(cons
     o.mir = nullptr; o.mir_ld = 0;
     msa_tile<TYPE>(planes, n, W32, dist_type, s_rid, s_cid, o, smem);
 }
+
+static const char* const kMsaUnknownType = "unknown distance type for a nucleotide alignment (valid: 1-6, 9 TN93, 10 LogDet, 11 paralinear)";
 
 static const double* msa_jc_tab(const MsaBuffers& m, int dist_type)
 {
@@ -562,7 +731,10 @@ static int msa_launch(int dist_type, hipStream_t s, const MsaBuffers& m, double*
     case DPR_DIST_K2P:       return launch_matrix<DPR_DIST_K2P>(g, s, m.planes, m.n, m.W32, dist_type, D, ld, rows, rank, world, row0, col0, ncols, transposed, nullptr, 0);
     case DPR_DIST_TAMURA:    return launch_matrix<DPR_DIST_TAMURA>(g, s, m.planes, m.n, m.W32, dist_type, D, ld, rows, rank, world, row0, col0, ncols, transposed, nullptr, 0);
     case DPR_DIST_JINNEI:    return launch_matrix<DPR_DIST_JINNEI>(g, s, m.planes, m.n, m.W32, dist_type, D, ld, rows, rank, world, row0, col0, ncols, transposed, nullptr, 0);
-    default: set_error("unknown distance type (valid: 1-6)"); return DPR_ERR_ARG;
+    case DPR_DIST_TN93:
+    case DPR_DIST_LOGDET:
+    case DPR_DIST_PARALINEAR: return launch_matrix<DPR_DIST_TN93>(g, s, m.planes, m.n, m.W32, dist_type, D, ld, rows, rank, world, row0, col0, ncols, transposed, nullptr, 0);
+    default: set_error(kMsaUnknownType); return DPR_ERR_ARG;
     }
 }
 
@@ -579,7 +751,10 @@ int msa_dist_jobs(const MsaBuffers& m, int dist_type, const PairJobs& J, int njo
     case DPR_DIST_K2P:       hipLaunchKernelGGL(msa_dist_jobs_kernel<DPR_DIST_K2P>, dim3(njobs), dim3(kThreads), 0, s, m.planes, m.n, m.W32, dist_type, J, (const double*)nullptr, 0, MsaSparseX{ nullptr }); break;
     case DPR_DIST_TAMURA:    hipLaunchKernelGGL(msa_dist_jobs_kernel<DPR_DIST_TAMURA>, dim3(njobs), dim3(kThreads), 0, s, m.planes, m.n, m.W32, dist_type, J, (const double*)nullptr, 0, MsaSparseX{ nullptr }); break;
     case DPR_DIST_JINNEI:    hipLaunchKernelGGL(msa_dist_jobs_kernel<DPR_DIST_JINNEI>, dim3(njobs), dim3(kThreads), 0, s, m.planes, m.n, m.W32, dist_type, J, (const double*)nullptr, 0, MsaSparseX{ nullptr }); break;
-    default: set_error("unknown distance type (valid: 1-6)"); return DPR_ERR_ARG;
+    case DPR_DIST_TN93:
+    case DPR_DIST_LOGDET:
+    case DPR_DIST_PARALINEAR: hipLaunchKernelGGL(msa_dist_jobs_kernel<DPR_DIST_TN93>, dim3(njobs), dim3(kThreads), 0, s, m.planes, m.n, m.W32, dist_type, J, (const double*)nullptr, 0, MsaSparseX{ nullptr }); break;
+    default: set_error(kMsaUnknownType); return DPR_ERR_ARG;
     }
     DPR_HIP(hipGetLastError());
     return DPR_OK;

@@ -72,6 +72,9 @@ static const char* distanceName(const Param& params)
     case DPR_DIST_K2P: return "K2P";
     case DPR_DIST_TAMURA: return "Tamura";
     case DPR_DIST_JINNEI: return "Jinnei";
+    case DPR_DIST_TN93: return "TN93";
+    case DPR_DIST_LOGDET: return "LogDet";
+    case DPR_DIST_PARALINEAR: return "paralinear";
     }
     return "unknown";
 }

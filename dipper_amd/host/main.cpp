@@ -59,6 +59,9 @@ static const char* kHelp =
     "                                6 - Jinnei\n"
     "                                7 - Poisson correction (--protein only)\n"
     "                                8 - Kimura 1983 (--protein only)\n"
+    "                                9 - TN93 (Tamura-Nei 1993; nucleotides only, as are 10 and 11)\n"
+    "                                10 - LogDet\n"
+    "                                11 - paralinear\n"
     "  -a [ --add ]                Add query to backbone using k-closest placement\n"
     "  -t [ --input-tree ] arg     Input backbone tree (Newick format), required with --add option\n"
     "  -h [ --help ]               Print this help message\n\n"

@@ -51,6 +51,22 @@ extern "C" {
  * Types 3-6 are nucleotide models (DPR_ERR_ARG on a protein alignment); 7-8 are DPR_ERR_ARG on a nucleotide alignment. */
 #define DPR_DIST_POISSON 7
 #define DPR_DIST_KIMURA 8
+/* nucleotide alignments only (dpr_set_msa; no reference counterpart; DPR_ERR_ARG on a protein alignment).  For the ordered pair
+ * (row a, column b), F[i][j] = the number of sites where a holds base i, b holds base j and both are bases; base order
+ * A, C, G, T = 0..3.  All integers: N = sum F, r_i = sum_j F[i][j], c_j = sum_i F[i][j], a_i = r_i + c_i.
+ *   9  TN93 (Tamura-Nei 1993): g_i = a_i / (2N), gR = gA + gG, gY = gC + gT, P1 = (F[A][G] + F[G][A]) / N,
+ *      P2 = (F[C][T] + F[T][C]) / N, Q = (N - trace F) / N - P1 - P2, k1 = 2 gA gG / gR, k2 = 2 gC gT / gY,
+ *      k3 = 2 (gR gY - gA gG gY / gR - gC gT gR / gY),
+ *      d = -k1 ln(1 - P1/k1 - Q/(2 gR)) - k2 ln(1 - P2/k2 - Q/(2 gY)) - k3 ln(1 - Q/(2 gR gY));
+ *      NaN when N = 0, a_A a_G = 0 or a_C a_T = 0; not finite when a logarithm's argument is <= 0.
+ *   10 LogDet (Lockhart 1994): d = -1/4 ln(det F / N^4) - ln 4; det F = 0 with N > 0 gives +inf, det F < 0 or N = 0 NaN.
+ *   11 paralinear (Lake 1994): d = -1/4 ln(det F / sqrt(prod_i r_i c_i)); det F < 0 gives NaN, det F = 0 gives +inf when
+ *      prod r_i c_i > 0, else NaN.
+ * det F is computed exactly in integers, and every value is a function of integers that do not change when a and b swap
+ * (a_i, F[i][j] + F[j][i], trace, N, det F, r_i c_i): D[a][b] and D[b][a] are the same bits however they are computed. */
+#define DPR_DIST_TN93 9
+#define DPR_DIST_LOGDET 10
+#define DPR_DIST_PARALINEAR 11
 
 /* error codes */
 #define DPR_OK 0
