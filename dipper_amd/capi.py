@@ -93,6 +93,10 @@ def load_library():
     L.dpr_ctx_set_nj_multi_plan.argtypes = [C.c_void_p, C.c_int]
     L.dpr_ctx_set_nj_virtual_shards.argtypes = [C.c_void_p, C.c_int]
     L.dpr_ctx_set_nj_kernel_timing.argtypes = [C.c_void_p, C.c_int]
+    L.dpr_ctx_set_nj_variant.argtypes = [C.c_void_p, C.c_int]
+    L.dpr_get_nj_lambda.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+    L.dpr_nj_variant_host.argtypes = [C.c_int, c_f64p, C.c_int64, C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p]
+    L.dpr_nj_variant_host.restype = C.c_int64
     L.dpr_get_nj_kernel_timing.argtypes = [C.c_void_p, C.POINTER(C.c_int), c_f64p, C.POINTER(C.c_int64)]
     L.dpr_nj_kernel_name.argtypes = [C.c_int]
     L.dpr_nj_kernel_name.restype = C.c_char_p
@@ -324,6 +328,29 @@ def transfer_taxa_host(n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi
     _chk(lib, lib.dpr_transfer_taxa_host(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), cutoff_permille,
                                          _p(phi_sum, c_i64p), _p(moved, c_i64p), _p(pairs, c_i64p)))
     return phi_sum, moved, pairs
+
+
+NJ_VARIANT_NJ, NJ_VARIANT_BIONJ = 0, 1
+
+
+def nj_variant_host(variant, D, max_iters=-1):
+    """The streaming loop restated on the host (no GPU): variant 0 NJ, 1 BIONJ.  D: (n, n) array whose strict lower triangle is
+    read.  dict(iters, merge_x, merge_y, bl_x, bl_y, last_d, lam): `iters` entries each; fewer than min(n - 2, max_iters) when an
+    iteration found no candidate; lam is all 0.5 for NJ"""
+    lib = load_library()
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    rows = np.ascontiguousarray(np.concatenate([D[i, :i] for i in range(n)])) if n > 1 else np.zeros(1)
+    k = max(n - 2, 1)
+    mx = np.zeros(k, dtype=np.int32)
+    my = np.zeros(k, dtype=np.int32)
+    bx = np.zeros(k, dtype=np.float64)
+    by = np.zeros(k, dtype=np.float64)
+    lam = np.full(k, 0.5, dtype=np.float64)
+    last = C.c_double(0.0)
+    done = _chk(lib, lib.dpr_nj_variant_host(variant, _p(rows, c_f64p), n, max_iters, _p(mx, c_i32p), _p(my, c_i32p), _p(bx, c_f64p),
+                                             _p(by, c_f64p), C.byref(last), _p(lam, c_f64p)))
+    return dict(iters=done, merge_x=mx[:done], merge_y=my[:done], bl_x=bx[:done], bl_y=by[:done], last_d=last.value, lam=lam[:done])
 
 
 def pack4_many(seqs):
@@ -649,6 +676,17 @@ class Dipper:
 
     def set_nj_virtual_shards(self, w):
         _chk(self.L, self.L.dpr_ctx_set_nj_virtual_shards(self.h, w))
+
+    def set_nj_variant(self, variant):
+        """0 = NJ (default), 1 = BIONJ; effective at the next dist_matrix / reserve_nj"""
+        _chk(self.L, self.L.dpr_ctx_set_nj_variant(self.h, variant))
+
+    def nj_lambda(self):
+        """lambda of the BIONJ iterations done since dist_matrix"""
+        out = np.zeros(max(self.n_total() - 2, 1), dtype=np.float64)
+        cnt = C.c_int64()
+        _chk(self.L, self.L.dpr_get_nj_lambda(self.h, _p(out, c_f64p), C.byref(cnt)))
+        return out[: cnt.value]
 
     def argmin_once(self, reps=1):
         i = C.c_int32()

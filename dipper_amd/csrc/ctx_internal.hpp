@@ -69,6 +69,8 @@ struct dpr_ctx {
     double dc_ms[3] = { 0, 0, 0 };   // backbone, cluster assignment, cluster trees
     // plan knobs of THIS context (dpr_ctx_set_*); -1 = follow the process-wide default (dpr_set_* / environment)
     int nj_mode = -1, nj_vshards = -1, nj_multi_plan = -1;
+    int nj_variant = 0;              // dpr_ctx_set_nj_variant: 0 NJ, 1 BIONJ; read by the next dpr_dist_matrix / dpr_reserve_nj
+    bool nj_bionj = false;           // the matrix of the last dpr_dist_matrix was set up for BIONJ (single-rank streaming plan, V beside D)
     int nj_adaptive = -1;            // adaptive pruned / streaming plan of the single-rank NJ (-1 = DPR_NJ_ADAPTIVE, default on)
     // row-sharded streaming NJ: exchange plan of the loop (-1 = DPR_NJ_EXCHANGE, default peer; see njs.hip) and what the
     // last dpr_dist_matrix actually set up (a failed peer set-up falls back to the legacy loop and says why)

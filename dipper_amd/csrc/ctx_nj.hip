@@ -1,5 +1,6 @@
 // C ABI, distance matrix and neighbor joining: plan selection (single GPU: pruned / streaming; several ranks: replicated,
 // unit-sharded, row-sharded streaming, row-sharded pruned), dpr_dist_matrix, dpr_nj_run, dpr_argmin_once and the NJ getters.
+// BIONJ (dpr_ctx_set_nj_variant): always the single-rank streaming plan; dpr_nj_variant_host restates the streaming loop on the host.
 #include "ctx_internal.hpp"
 
 namespace dpr {
@@ -75,6 +76,14 @@ static std::vector<NjBuffers*> njr_ranks(dpr_ctx* c)
 // one NJ iteration (active size n, iteration index it) on every rank held by this context
 static int nj_iteration(dpr_ctx* c, int64_t n, int64_t it)
 {
+    if (c->nj_bionj) {
+        // BIONJ: this rank's own copy whatever the world; the lambda kernel reads the rows of V that the update rewrites
+        NjBuffers& b = c->nj[0];
+        if (int rc = nj_launch_scan(b, false, n, it, c->stream)) return rc;
+        if (int rc = nj_launch_bionj_lambda(b, n, c->stream)) return rc;
+        c->nj_launches += 3;
+        return nj_launch_bionj_post(b, n, it, c->stream);
+    }
     if (c->world == 1) {
         NjBuffers& b = c->nj[0];
         if (int rc = nj_launch_scan(b, false, n, it, c->stream)) return rc;
@@ -135,16 +144,25 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
         set_error("dpr_dist_matrix: source not available");
         return DPR_ERR_ARG;
     }
+    // BIONJ (dpr_ctx_set_nj_variant): the single-rank streaming plan on this rank's own copy of the matrix, whatever the
+    // NJ mode, the adaptive switch and the multi-rank plans say
+    const bool bionj = c->nj_variant == 1;
+    if (bionj && (c->vworld > 0 || ctx_vshards(c) > 1)) {
+        set_error("dpr_dist_matrix: BIONJ runs the single-rank streaming plan: not on a context of virtual ranks or with virtual shards (dpr_set_nj_virtual_shards > 1)");
+        return DPR_ERR_ARG;
+    }
     c->have_matrix = 0;
+    c->nj_bionj = bionj;
     // Several real ranks + pruned NJ: every rank builds and keeps the WHOLE matrix (7.2 GB at 30 000 tips, 80 GB at
     // 100 000) and the ranks share the per-iteration unit tests and scans (njp.hip, unit-sharded mode).  The
     // streaming algorithm (DPR_NJ_MODE=stream) keeps the row-sharded layout.
-    const bool njr = ctx_njr(c, n);
-    const bool repl = !njr && c->world > 1 && c->vworld == 0 && want_pruned(c) && n >= 3;
+    const bool njr = !bionj && ctx_njr(c, n);
+    const bool repl = bionj ? c->world > 1 : (!njr && c->world > 1 && c->vworld == 0 && want_pruned(c) && n >= 3);
     c->nj_replicated = repl;
+    if (bionj) c->nj_unit_sharded = false;
     c->nj_row_pruned = false;
     for (size_t r = 0; r < c->nj.size(); ++r)
-        if (int rc = nj_alloc(c->nj[r], n, repl ? 0 : (c->vworld > 0 ? (int)r : c->rank), repl ? 1 : c->world, c->stream, njr ? njr_twin_rows(n, c->world) : 0)) return rc;
+        if (int rc = nj_alloc(c->nj[r], n, repl ? 0 : (c->vworld > 0 ? (int)r : c->rank), repl ? 1 : c->world, c->stream, njr ? njr_twin_rows(n, c->world) : 0, bionj)) return rc;
     const bool row_sharded = c->world > 1 && !repl;
     if (row_sharded) { if (int rc = njs_setup(c, njr)) return rc; }
     else c->nj_exchange_active = kNjsLegacy;
@@ -169,6 +187,8 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
         } else {
             if (int rc = nj_expand_lower(b, c->packed_lower, c->stream)) return rc;
         }
+        if (bionj)
+            if (int rc = nj_bionj_init(b, c->stream)) return rc;
         // row sums of the own rows: into U (one rank), the slice of the legacy exchange, or the window's slice (peer plans)
         double* sums = !row_sharded ? nullptr : peer_plan ? reinterpret_cast<double*>(b.peer.win + b.peer.lay.off_slice) : b.slice;
         if (int rc = nj_init_sums(b, c->stream, sums)) return rc;
@@ -207,7 +227,7 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
         c->nj_row_pruned = true;
         c->nj_exchange_note = std::string("row-sharded pruned NJ (njr.hip), exchange plan ") + (rplan == kNjrMailbox ? "mailbox" : "collective");
     }
-    if ((c->world == 1 || repl) && want_pruned(c) && n >= 3) {
+    if (!bionj && (c->world == 1 || repl) && want_pruned(c) && n >= 3) {
         NjPruned& q = c->nj[0].pr;
         const int plan = ctx_multi_plan(c);
         const bool shard = repl && (plan == 1 || (plan == 0 && n >= kNjShardTips));
@@ -233,11 +253,16 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
 int dpr_reserve_nj(dpr_ctx* c, int64_t n)
 {
     if (!c || n < 2 || n >= (1 << 24)) { set_error("dpr_reserve_nj: bad argument"); return DPR_ERR_ARG; }
-    if (c->world != 1 || c->vworld > 0) return DPR_OK;
+    const bool bionj = c->nj_variant == 1;
+    if (bionj && (c->vworld > 0 || ctx_vshards(c) > 1)) {
+        set_error("dpr_reserve_nj: BIONJ runs the single-rank streaming plan: not on a context of virtual ranks or with virtual shards (dpr_set_nj_virtual_shards > 1)");
+        return DPR_ERR_ARG;
+    }
+    if ((c->world != 1 && !bionj) || c->vworld > 0) return DPR_OK;
     DPR_HIP(hipSetDevice(c->device));
     c->have_matrix = 0;
-    if (int rc = nj_alloc(c->nj[0], n, 0, 1, c->stream)) return rc;
-    if (want_pruned(c) && n >= 3) {
+    if (int rc = nj_alloc(c->nj[0], n, 0, 1, c->stream, 0, bionj)) return rc;
+    if (!bionj && want_pruned(c) && n >= 3) {
         NjPruned& q = c->nj[0].pr;
         if (ctx_vshards(c) > 1) { q.sh_world = ctx_vshards(c); q.sh_rank = 0; q.sh_virtual = true; }
         if (int rc = njp_arena(q, n, c->stream)) return rc;
@@ -399,7 +424,7 @@ int64_t dpr_nj_run(dpr_ctx* c, int64_t max_iters, int32_t* merge_x, int32_t* mer
             int32_t pos01[2];
             DPR_HIP(hipMemcpy(pos01, b0.pr.pos_of_slot, sizeof(pos01), hipMemcpyDeviceToHost));
             DPR_HIP(hipMemcpy(last_d, b0.pr.D + (int64_t)pos01[1] * b0.pr.ld + pos01[0], sizeof(double), hipMemcpyDeviceToHost));
-        } else if (c->world == 1 || c->vworld > 0) {
+        } else if (c->world == 1 || c->vworld > 0 || c->nj_bionj) {
             DPR_HIP(hipMemcpy(last_d, b0.D + 1 * b0.ld + 0, sizeof(double), hipMemcpyDeviceToHost));
         } else if (peer_plan && !b0.peer.h_D.empty()) {
             // rank 0's row 1 through the mapping of its matrix (its flush is behind the barrier above)
@@ -478,7 +503,8 @@ int dpr_get_nj_multi_info(dpr_ctx* c, char* buf, int cap)
     if (!c || !buf || cap <= 0) { set_error("dpr_get_nj_multi_info: bad argument"); return DPR_ERR_ARG; }
     static const char* const ex[] = { "legacy (two all-gathers per iteration)", "peer (one all-gather, rows pulled)", "mailbox (no collective)" };
     std::string s;
-    if (c->world <= 1) s = "single rank";
+    if (c->nj_bionj && c->world > 1) s = "BIONJ, streaming, every rank its own copy";
+    else if (c->world <= 1) s = "single rank";
     else if (c->nj_row_pruned) s = c->nj_exchange_note;
     else if (c->nj_replicated) s = c->nj_unit_sharded ? "pruned, matrix replicated, unit tests and scans sharded (one all-gather of block records per iteration)"
                                                        : "pruned, every rank runs the single-GPU plan on its own copy of the matrix (replicas)";
@@ -499,6 +525,24 @@ int dpr_ctx_set_nj_multi_plan(dpr_ctx* c, int plan)
 {
     if (!c || plan < -1 || plan > 3) { set_error("dpr_ctx_set_nj_multi_plan: -1 default, 0 auto, 1 unit-sharded, 2 single-GPU plan on every rank, 3 row-sharded pruned"); return DPR_ERR_ARG; }
     c->nj_multi_plan = plan;
+    return DPR_OK;
+}
+// 0 = NJ, 1 = BIONJ (include/dipper_hip.h); read by the context's next dpr_dist_matrix / dpr_reserve_nj
+int dpr_ctx_set_nj_variant(dpr_ctx* c, int variant)
+{
+    if (!c || variant < 0 || variant > 1) { set_error("dpr_ctx_set_nj_variant: variant must be 0 (NJ) or 1 (BIONJ)"); return DPR_ERR_ARG; }
+    c->nj_variant = variant;
+    return DPR_OK;
+}
+int dpr_get_nj_lambda(dpr_ctx* c, double* out, int64_t* count)
+{
+    if (!c || !count) { set_error("dpr_get_nj_lambda: null argument"); return DPR_ERR_ARG; }
+    if (!c->have_matrix || !c->nj_bionj || !c->nj[0].log_lam) { set_error("dpr_get_nj_lambda: no BIONJ matrix (dpr_ctx_set_nj_variant(ctx, 1), then dpr_dist_matrix)"); return DPR_ERR_STATE; }
+    DPR_HIP(hipSetDevice(c->device));
+    NjState st;
+    if (int rc = fetch_state(c, &st)) return rc;
+    *count = st.it;
+    if (out && st.it > 0) DPR_HIP(hipMemcpy(out, c->nj[0].log_lam, sizeof(double) * (size_t)st.it, hipMemcpyDeviceToHost));
     return DPR_OK;
 }
 // Per-kernel timing of the pruned NJ loop: stride > 0 makes the following dpr_nj_run calls enqueue their iterations
@@ -581,6 +625,143 @@ int dpr_get_nj_progress(dpr_ctx* c, int64_t* iterations_done, int64_t* active)
     if (iterations_done) *iterations_done = st.it;
     if (active) *active = st.n;
     return DPR_OK;
+}
+
+// ---- host-only restatement of the streaming loop, NJ and BIONJ (the contract is in include/dipper_hip.h) --------------------
+}  // extern "C" (helpers)
+namespace {
+// pairwise tree over 256 values, c[t] += c[t + s] for s = 128 .. 1 (block_tree256 of the kernels)
+double host_tree256(double* c)
+{
+    for (int s = 128; s > 0; s >>= 1)
+        for (int t = 0; t < s; ++t) c[t] = c[t] + c[t + s];
+    return c[0];
+}
+// chunk partials folded by 256 classes (ascending), then the tree (finish_ux of the kernels)
+double host_fold(const double* part, int64_t nchunk)
+{
+    double p[256];
+    for (int t = 0; t < 256; ++t) {
+        double acc = 0.0;
+        for (int64_t c = t; c < nchunk; c += 256) acc += part[c];
+        p[t] = acc;
+    }
+    return host_tree256(p);
+}
+}  // namespace
+extern "C" {
+
+int64_t dpr_nj_variant_host(int variant, const double* lower_rows, int64_t N, int64_t max_iters, int32_t* merge_x, int32_t* merge_y,
+                            double* bl_x, double* bl_y, double* last_d, double* lambda)
+{
+    if ((variant != 0 && variant != 1) || N < 2 || N >= (1 << 24) || (N > 2 && (!lower_rows || !merge_x || !merge_y || !bl_x || !bl_y))) {
+        set_error("dpr_nj_variant_host: bad argument");
+        return DPR_ERR_ARG;
+    }
+    const bool bionj = variant == 1;
+    const int64_t ld = N;
+    std::vector<double> D((size_t)(N * ld), 0.0), V, U((size_t)N), Ur((size_t)N), part((size_t)((N + 255) / 256 + 1));
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t j = 0; j < i; ++j) D[(size_t)(i * ld + j)] = D[(size_t)(j * ld + i)] = lower_rows[i * (i - 1) / 2 + j];
+    if (bionj) V = D;
+    // initial row sums: 256 class partials (j == t mod 256, ascending, j != i), the tree
+    for (int64_t i = 0; i < N; ++i) {
+        double c[256];
+        for (int t = 0; t < 256; ++t) {
+            double acc = 0.0;
+            for (int64_t j = t; j < N; j += 256)
+                if (j != i) acc += D[(size_t)(i * ld + j)];
+            c[t] = acc;
+        }
+        U[(size_t)i] = host_tree256(c);
+    }
+    int64_t it = 0;
+    for (; it < N - 2; ++it) {
+        if (max_iters >= 0 && it >= max_iters) break;
+        const int64_t n = N - it, last = n - 1, nchunk = (n + 255) / 256;
+        const double r = (double)(n - 2);
+        for (int64_t i = 0; i < n; ++i) Ur[(size_t)i] = U[(size_t)i] / r;
+        // selection: both orientations of every element of the strict lower triangle, strict '<' on q, ties by key
+        double bq = 10000.0;
+        uint64_t bk = ~0ull;
+        for (int64_t a = 1; a < n; ++a) {
+            const double* row = D.data() + a * ld;
+            const double ua = Ur[(size_t)a];
+            for (int64_t c = 0; c < a; ++c) {
+                const double dv = row[c], uc = Ur[(size_t)c];
+                const double q1 = (dv - ua) - uc, q2 = (dv - uc) - ua;
+                if (q1 <= bq) { const uint64_t k = dpr_nj_key(a, c, n); if (q1 < bq || k < bk) { bq = q1; bk = k; } }
+                if (q2 <= bq) { const uint64_t k = dpr_nj_key(c, a, n); if (q2 < bq || k < bk) { bq = q2; bk = k; } }
+            }
+        }
+        if (bk == ~0ull || !(bq < 10000.0)) break;     // no candidate
+        const int64_t ki = (int64_t)(bk & 0xFFFFFFull), kj = (int64_t)((bk >> 24) & 0xFFFFFFull);
+        const int64_t x = ki < kj ? ki : kj, y = ki < kj ? kj : ki;
+        const double d = D[(size_t)(y * ld + x)];
+        const double bx0 = (d + U[(size_t)x] / r - U[(size_t)y] / r) * 0.5, by0 = d - bx0;
+        double blX = bx0, blY = by0;
+        if (blX < 0) { blY += blX; blX = 0; }
+        if (blY < 0) { blX += blY; blY = 0; }
+        merge_x[it] = (int32_t)x; merge_y[it] = (int32_t)y; bl_x[it] = blX; bl_y[it] = blY;
+        double lam = 0.5, vxy = 0.0;
+        if (bionj) {
+            vxy = V[(size_t)(y * ld + x)];
+            for (int64_t c = 0; c < nchunk; ++c) {
+                double v[256];
+                for (int t = 0; t < 256; ++t) {
+                    const int64_t k = c * 256 + t;
+                    v[t] = (k < n && k != x && k != y) ? V[(size_t)(y * ld + k)] - V[(size_t)(x * ld + k)] : 0.0;
+                }
+                part[(size_t)c] = host_tree256(v);
+            }
+            const double ssum = host_fold(part.data(), nchunk);
+            lam = 0.5 + ssum / (2.0 * r * vxy);
+            if (vxy == 0.0 || lam != lam) lam = 0.5;
+            else if (lam < 0.0) lam = 0.0;
+            else if (lam > 1.0) lam = 1.0;
+            if (lambda) lambda[it] = lam;
+        }
+        // update: slot i < n, i not x or y; the new node takes slot x, the last slot moves to y
+        for (int64_t c = 0; c < nchunk; ++c) {
+            double v[256];
+            for (int t = 0; t < 256; ++t) {
+                const int64_t i = c * 256 + t;
+                double val = 0.0;
+                if (i < n && i != x && i != y) {
+                    const double dxi = D[(size_t)(x * ld + i)], dyi = D[(size_t)(y * ld + i)];
+                    double vnew = 0.0;
+                    if (bionj) {
+                        const double vxi = V[(size_t)(x * ld + i)], vyi = V[(size_t)(y * ld + i)];
+                        const double a = dxi - bx0, b = dyi - by0;
+                        val = b + lam * (a - b);
+                        vnew = vyi + lam * (vxi - vyi) - (lam * (1.0 - lam)) * vxy;
+                    } else {
+                        val = (dxi + dyi - d) * 0.5;
+                    }
+                    if (i != last) {
+                        const double far = D[(size_t)(last * ld + i)];
+                        U[(size_t)i] = U[(size_t)i] + (-dxi - dyi + val);
+                        D[(size_t)(x * ld + i)] = val; D[(size_t)(i * ld + x)] = val;
+                        D[(size_t)(y * ld + i)] = far; D[(size_t)(i * ld + y)] = far;
+                        if (bionj) {
+                            const double vfar = V[(size_t)(last * ld + i)];
+                            V[(size_t)(x * ld + i)] = vnew; V[(size_t)(i * ld + x)] = vnew;
+                            V[(size_t)(y * ld + i)] = vfar; V[(size_t)(i * ld + y)] = vfar;
+                        }
+                    } else {
+                        U[(size_t)y] = U[(size_t)last] + (-dxi - dyi + val);
+                        D[(size_t)(x * ld + y)] = val; D[(size_t)(y * ld + x)] = val;
+                        if (bionj) { V[(size_t)(x * ld + y)] = vnew; V[(size_t)(y * ld + x)] = vnew; }
+                    }
+                }
+                v[t] = val;
+            }
+            part[(size_t)c] = host_tree256(v);
+        }
+        U[(size_t)x] = host_fold(part.data(), nchunk);
+    }
+    if (it == N - 2 && last_d) *last_d = D[(size_t)(1 * ld + 0)];
+    return it;
 }
 
 int dpr_get_njp_shape(dpr_ctx* c, int64_t* positions, int* row_groups, int* strips, int* post2, int* scan_grid)

@@ -310,13 +310,21 @@ struct NjBuffers {
     int32_t* log_y = nullptr;
     double* log_bx = nullptr;
     double* log_by = nullptr;
+    // BIONJ (dpr_ctx_set_nj_variant(ctx, 1); nullptr while the context builds NJ trees)
+    double* V = nullptr;       // variances: layout and row stride of D, a copy of D (pads included) once the distance source has filled it
+    double* vpart = nullptr;   // [ceil(N/256)] chunk partials of the lambda sum of the current iteration
+    double* bj = nullptr;      // [4] unclamped bx0, by0 and vxy = V[y][x] of the current iteration (nj_bionj_lambda_kernel -> nj_bionj_post_kernel)
+    double* log_lam = nullptr; // [N] lambda of every iteration, beside the merge log
     int rank = 0, world = 1;
     NjPruned pr;
     NjRowShard rs;
 };
 
 // nj.hip
-int nj_alloc(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows = 0);   // fills ordered on s; same shape again: buffers kept
+int nj_alloc(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows = 0, bool bionj = false);   // fills ordered on s; same shape again: buffers kept (bionj: + V and its vectors; without: they are released)
+int nj_bionj_init(NjBuffers& b, hipStream_t s);                                      // V = D (the whole buffer), once the distance source has filled D
+int nj_launch_bionj_lambda(NjBuffers& b, int64_t n, hipStream_t s);                  // chunk partials of the lambda sum, bx0 / by0 / vxy
+int nj_launch_bionj_post(NjBuffers& b, int64_t n, int64_t it, hipStream_t s);        // select + commit + weighted update of D, V, U
 int nj_fill_pads(double* D, int64_t ld, int64_t nrows, int64_t ncols, int64_t rows_alloc, int64_t tail, bool diag, hipStream_t s);
 void nj_free(NjBuffers& b);
 int nj_expand_lower(NjBuffers& b, const double* d_packed_lower, hipStream_t s);

@@ -2,6 +2,7 @@
 // matrix/row-sum update.  Replaces src/neighborJoining.cu (calculateU :94-115, findMinDist
 // :117-148, thrust::min_element :214, host bookkeeping :219-239, updateDisMatrix :161-194) of the
 // reference with a device-resident loop: no host round trip per iteration.
+// BIONJ (no reference counterpart) runs the same scan with a lambda kernel and a weighted update (nj_bionj_*_kernel).
 //
 // Data layout in HBM: D is row-major fp64, full symmetric, row stride ld (multiple of 16 doubles =
 // 128 B).  A rank stores the rows it owns (block-cyclic, 64 rows per block) at full width.
@@ -269,6 +270,121 @@ __global__ __launch_bounds__(kThreads) void nj_post_kernel(double* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
+// BIONJ (world == 1; the contract is in include/dipper_hip.h).  Per iteration: scan (unchanged) -> lambda -> post.
+// The weight lambda needs a sum over the rows x and y of V, which the update rewrites; so does every thread's bx0 / by0
+// (U[y], which the tail thread rewrites) and vxy = V[y][x] (the tail thread again).  All three are read by a kernel of
+// their own, launched before the update: no block of the update can overtake a reader.
+// ------------------------------------------------------------------------------------------------
+// chunk partials of s (one block per 256 slots, thread k: t_k) -> vpart; block 0 also leaves bx0, by0, vxy in bj
+__global__ __launch_bounds__(kThreads) void nj_bionj_lambda_kernel(const double* __restrict__ V, int64_t ld,
+                                                                   const NjState* __restrict__ st, const double* __restrict__ U,
+                                                                   const NjRecord* __restrict__ partials, int nparts, int64_t n,
+                                                                   double* __restrict__ vpart, double* __restrict__ bj)
+{
+    __shared__ double s[kThreads];
+    __shared__ double sq[kThreads / 64], sdd[kThreads / 64];
+    __shared__ uint64_t sk[kThreads / 64];
+    if (st->status != 0) return;
+    if ((int64_t)blockIdx.x * kThreads >= n) return;
+    double bq, d; uint64_t bk;
+    reduce_records(partials, nparts, bq, bk, d, sq, sk, sdd);
+    if (bk == ~0ull || !(bq < 10000.0)) return;     // no candidate: the post kernel sets the status
+    const int64_t ki = (int64_t)(bk & 0xFFFFFFull), kj = (int64_t)((bk >> 24) & 0xFFFFFFull);
+    const int64_t x = ki < kj ? ki : kj, y = ki < kj ? kj : ki;
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    double t = 0.0;
+    if (k < n && k != x && k != y) t = V[y * ld + k] - V[x * ld + k];
+    const double cs = block_tree256(t, s);
+    if (threadIdx.x == 0) {
+        vpart[blockIdx.x] = cs;
+        if (blockIdx.x == 0) {
+            const double r = (double)(n - 2);
+            const double bx0 = (d + U[x] / r - U[y] / r) * 0.5;
+            bj[0] = bx0;
+            bj[1] = d - bx0;
+            bj[2] = V[y * ld + x];
+        }
+    }
+}
+
+// nj_post_kernel with the weighted update: thread i handles slot i of D and of V
+__global__ __launch_bounds__(kThreads) void nj_bionj_post_kernel(double* __restrict__ D, double* __restrict__ V, int64_t ld,
+                                                                 NjState* __restrict__ st, double* __restrict__ U,
+                                                                 double* __restrict__ Ur, uint64_t* __restrict__ KA,
+                                                                 double* __restrict__ xpart, const double* __restrict__ vpart,
+                                                                 const double* __restrict__ bj,
+                                                                 const NjRecord* __restrict__ partials, int nparts,
+                                                                 int64_t n, int64_t it, int32_t* __restrict__ log_x,
+                                                                 int32_t* __restrict__ log_y, double* __restrict__ log_bx,
+                                                                 double* __restrict__ log_by, double* __restrict__ log_lam)
+{
+    __shared__ double s[kThreads], sl[kThreads];
+    __shared__ double sq[kThreads / 64], sdd[kThreads / 64];
+    __shared__ uint64_t sk[kThreads / 64];
+    if (st->status != 0) return;
+    if ((int64_t)blockIdx.x * kThreads >= n) return;  // whole block idle
+    double bq, d; uint64_t bk;
+    reduce_records(partials, nparts, bq, bk, d, sq, sk, sdd);
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t last = n - 1;
+    if (bk == ~0ull || !(bq < 10000.0)) {
+        if (i == last) st->status = 1;
+        return;
+    }
+    const int64_t ki = (int64_t)(bk & 0xFFFFFFull), kj = (int64_t)((bk >> 24) & 0xFFFFFFull);
+    const int64_t x = ki < kj ? ki : kj, y = ki < kj ? kj : ki;
+    const int64_t n1 = n - 1;
+    const double r1 = (double)(n1 - 2);
+
+    // lambda: every block finishes the sum for itself (the canonical fold of the chunk partials, as U[x])
+    const double ssum = finish_ux_bcast(vpart, n, sl);
+    const double bx0 = bj[0], by0 = bj[1], vxy = bj[2];
+    const double r = (double)(n - 2);
+    double lam = 0.5 + ssum / (2.0 * r * vxy);
+    if (vxy == 0.0 || lam != lam) lam = 0.5;
+    else if (lam < 0.0) lam = 0.0;
+    else if (lam > 1.0) lam = 1.0;
+
+    double val = 0.0;
+    if (i == last) {
+        commit_merge(st, U, n, it, x, y, d, bq, log_x, log_y, log_bx, log_by);  // reads U[y] before the tail rewrites it
+        log_lam[it] = lam;
+    }
+    if (i < n && i != x && i != y) {
+        const double dxi = D[x * ld + i], dyi = D[y * ld + i];
+        const double vxi = V[x * ld + i], vyi = V[y * ld + i];
+        const double a = dxi - bx0, b = dyi - by0;
+        val = b + lam * (a - b);
+        const double vnew = vyi + lam * (vxi - vyi) - (lam * (1.0 - lam)) * vxy;
+        if (i != last) {
+            const double far = D[last * ld + i], vfar = V[last * ld + i];
+            const double u = U[i] + (-dxi - dyi + val);
+            U[i] = u;
+            Ur[i] = u / r1;
+            D[x * ld + i] = val;
+            D[i * ld + x] = val;
+            D[y * ld + i] = far;
+            D[i * ld + y] = far;
+            V[x * ld + i] = vnew;
+            V[i * ld + x] = vnew;
+            V[y * ld + i] = vfar;
+            V[i * ld + y] = vfar;
+        } else {
+            const double uy = U[last] + (-dxi - dyi + val);
+            U[y] = uy;
+            Ur[y] = uy / r1;
+            D[x * ld + y] = val;
+            D[y * ld + x] = val;
+            V[x * ld + y] = vnew;
+            V[y * ld + x] = vnew;
+        }
+    }
+    if (i < n1) KA[i] = nj_key_a_dev(i, n1);
+    const double cs = block_tree256(val, s);
+    if (threadIdx.x == 0) xpart[blockIdx.x] = cs;
+}
+
+// ------------------------------------------------------------------------------------------------
 // world > 1.  Per iteration: scan -> local record -> all-gather -> commit (identical on every rank)
 // + column slices of x, y, n-1 for the owned rows -> all-gather -> sharded update.
 // ------------------------------------------------------------------------------------------------
@@ -446,16 +562,24 @@ int nj_fill_pads(double* D, int64_t ld, int64_t nrows, int64_t ncols, int64_t ro
 // A context that builds a matrix of the same shape again (bench.py's steps, a second dpr_dist_matrix) keeps every
 // buffer: freeing and re-allocating 2 x 7.2 GB per call at 30 000 tips cost more than the distance kernel itself.
 // Only the pads are zeroed then -- every element of the n x n block is overwritten by the distance kernels.
-static int nj_alloc_inner(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows);
-int nj_alloc(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows)
+static int nj_alloc_inner(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows, bool bionj);
+int nj_alloc(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows, bool bionj)
 {
     // a failure part-way (out of memory after the matrix) must not leave a half-built NjBuffers behind: the reuse test
     // of the next call looks at b.D only (dpr_reserve_nj is called best-effort by the CLI, its return code ignored)
-    const int rc = nj_alloc_inner(b, N, rank, world, s, twin_rows);
+    const int rc = nj_alloc_inner(b, N, rank, world, s, twin_rows, bionj);
     if (rc != DPR_OK) nj_free(b);
     return rc;
 }
-static int nj_alloc_inner(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows)
+// the BIONJ buffers of a context that has gone back to NJ (a second n x n matrix)
+static void nj_free_bionj(NjBuffers& b)
+{
+    void* ptrs[] = { b.V, b.vpart, b.bj, b.log_lam };
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    b.V = nullptr; b.vpart = nullptr; b.bj = nullptr; b.log_lam = nullptr;
+}
+static int nj_alloc_inner(NjBuffers& b, int64_t N, int rank, int world, hipStream_t s, int64_t twin_rows, bool bionj)
 {
     const bool reuse = b.D != nullptr && b.N == N && b.rank == rank && b.world == world && b.twin_rows == twin_rows;
     if (!reuse) {
@@ -505,6 +629,20 @@ static int nj_alloc_inner(NjBuffers& b, int64_t N, int rank, int world, hipStrea
         // the rows [0, rows_local) x [0, N) are rewritten by the producers; zero what they leave alone
         if (int rc = nj_fill_pads(b.D, b.ld, b.rows_local, N, rows_alloc, kTileCols + 16, world == 1, s)) return rc;
     }
+    // BIONJ: V (every byte of it is written by nj_bionj_init once D is filled) and its vectors; a context back on NJ gives them up
+    if (!bionj) nj_free_bionj(b);
+    else {
+        const size_t xcnt = (size_t)((N + kThreads - 1) / kThreads + 1);
+        if (!b.V) {
+            DPR_HIP(hipMalloc(&b.V, hbytes));
+            DPR_HIP(hipMalloc(&b.vpart, sizeof(double) * xcnt));
+            DPR_HIP(hipMalloc(&b.bj, sizeof(double) * 4));
+            DPR_HIP(hipMalloc(&b.log_lam, sizeof(double) * (size_t)(N + 1)));
+        }
+        DPR_HIP(hipMemsetAsync(b.vpart, 0, sizeof(double) * xcnt, s));
+        DPR_HIP(hipMemsetAsync(b.bj, 0, sizeof(double) * 4, s));
+        DPR_HIP(hipMemsetAsync(b.log_lam, 0, sizeof(double) * (size_t)(N + 1), s));
+    }
     DPR_HIP(hipMemsetAsync(b.U, 0, vec * sizeof(double), s));
     DPR_HIP(hipMemsetAsync(b.Ur, 0, vec * sizeof(double), s));
     DPR_HIP(hipMemsetAsync(b.KA, 0, vec * sizeof(uint64_t), s));
@@ -522,7 +660,7 @@ void nj_free(NjBuffers& b)
     njp_free(b.pr);
     njs_free_window(b);
     void* ptrs[] = { b.D, b.U, b.Ur, b.KA, b.partials, b.recs, b.recs64, b.xpart, b.gath, b.slice, b.st,
-                     b.log_x, b.log_y, b.log_bx, b.log_by };
+                     b.log_x, b.log_y, b.log_bx, b.log_by, b.V, b.vpart, b.bj, b.log_lam };
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     const NjPeer keep = b.peer;      // (the plan and the poll limit are settings of the context, not of an allocation)
@@ -614,6 +752,32 @@ int nj_launch_post(NjBuffers& b, int64_t n, int64_t it, hipStream_t s)
     const unsigned grid = (unsigned)((n + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(nj_post_kernel, dim3(grid), dim3(kThreads), 0, s, b.D, b.ld, b.st, b.U, b.Ur, b.KA, b.xpart,
                        b.partials, nj_scan_grid(), n, it, b.log_x, b.log_y, b.log_bx, b.log_by);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+// BIONJ: V = D, pads included (one device copy of the whole buffer behind the distance source, ahead of the row sums)
+int nj_bionj_init(NjBuffers& b, hipStream_t s)
+{
+    if (!b.V || b.world != 1 || b.twin_rows != 0) { set_error("nj_bionj_init: no BIONJ buffers"); return DPR_ERR_STATE; }
+    DPR_HIP(hipMemcpyAsync(b.V, b.D, b.half_bytes, hipMemcpyDeviceToDevice, s));
+    return DPR_OK;
+}
+
+int nj_launch_bionj_lambda(NjBuffers& b, int64_t n, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((n + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(nj_bionj_lambda_kernel, dim3(grid), dim3(kThreads), 0, s, b.V, b.ld, b.st, b.U, b.partials, nj_scan_grid(), n,
+                       b.vpart, b.bj);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
+int nj_launch_bionj_post(NjBuffers& b, int64_t n, int64_t it, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((n + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(nj_bionj_post_kernel, dim3(grid), dim3(kThreads), 0, s, b.D, b.V, b.ld, b.st, b.U, b.Ur, b.KA, b.xpart, b.vpart,
+                       b.bj, b.partials, nj_scan_grid(), n, it, b.log_x, b.log_y, b.log_bx, b.log_by, b.log_lam);
     DPR_HIP(hipGetLastError());
     return DPR_OK;
 }

@@ -12,9 +12,16 @@
 
 namespace dipper {
 
+bool& bionjOption()
+{
+    static bool on = false;
+    return on;
+}
+
 DeviceContext::DeviceContext(int device)
 {
     gpuCheck(dpr_create(&ctx, device), "dpr_create");
+    if (bionjOption()) gpuCheck(dpr_ctx_set_nj_variant(ctx, 1), "dpr_ctx_set_nj_variant");
     // one of several ranks (startRanks): join the others before any input reaches the device
     const RankInfo& ri = rankInfo();
     if (ri.world > 1) gpuCheck(dpr_comm_init_shared(ctx, ri.rank, ri.world, ri.region, DPR_COMM_SHARED_BYTES, ri.transport), "dpr_comm_init_shared");

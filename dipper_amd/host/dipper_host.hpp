@@ -129,6 +129,9 @@ void startRanks(const RankOptions& o, int base_device);
 // rank 0's closing line of a multi-rank run: "Ranks: G (transport, N device collectives; NJ plan ...)"; nothing with one rank
 void printRankSummary(dpr_ctx* ctx);
 
+// --bionj: every context this command creates builds BIONJ trees (dpr_ctx_set_nj_variant); set by main() before the first one
+bool& bionjOption();
+
 struct DeviceContext {  // replaces cudaSetDevice (src/tree_generation.cu:240-245)
     dpr_ctx* ctx = nullptr;
     explicit DeviceContext(int device);

@@ -82,6 +82,12 @@ static const char* kHelp =
     "                              over the sites where both sequences hold a residue.  -d 1 (p-distance,\n"
     "                              default), 2 (JC with 20 states), 7 or 8; conventional NJ, placement,\n"
     "                              --add and -o d / -o j; not with --bootstrap or divide-and-conquer\n"
+    "  --bionj                     Build the tree with BIONJ (Gascuel 1997) instead of NJ: the same pair\n"
+    "                              selection and branch lengths; the distances of a new node are a\n"
+    "                              variance-weighted mean of its children's.  Wherever conventional NJ\n"
+    "                              builds the tree (-m 2, or -m 0 below 30000; -i d, m or r; --protein;\n"
+    "                              every -d); with --bootstrap the main tree and every replicate tree are\n"
+    "                              BIONJ trees.  Not with -m 1, -m 3, --add, -o d or -o j\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -110,6 +116,7 @@ static const Opt kOpts[] = {
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
+    { "bionj", 0, false },
 };
 
 static void usageError(const std::string& what)
@@ -286,6 +293,15 @@ int main(int argc, char** argv)
     }
     for (const char* req : { "input-format", "input-file", "output-file" })
         if (!vm.count(req)) usageError(std::string("the option '--") + req + "' is required but missing");
+    // --bionj: what the arguments alone decide, before any input is read or a GPU touched
+    const bool bionj = vm.count("bionj") != 0;
+    if (bionj) {
+        const std::string al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
+        if (al == "1" || al == "3") usageError("--bionj needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add")) usageError("--bionj is not supported with --add");
+        if (out == "d" || out == "j") usageError("--bionj needs tree output (-o t)");
+        bionjOption() = true;      // every context of this command builds BIONJ trees (DeviceContext, the bootstrap's rank-local one)
+    }
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
     // --protein: what the arguments alone decide, before any input is read or a GPU touched
@@ -643,6 +659,9 @@ int main(int argc, char** argv)
         if (boot.replicates > 0 && pick_mode((long long)numSequences) != 2)
             die("ERROR: --bootstrap needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (bionj && pick_mode((long long)numSequences) != 2)
+            die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (protein && pick_mode((long long)numSequences) == 3)
             die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
                 " sequences select it in the default mode; use -m 1 or -m 2");
@@ -709,7 +728,7 @@ int main(int argc, char** argv)
             kplacementDeviceArrays.printTree(names, *output_);
             std::cerr << "Tree Created in: " << tree_ms << " ms\n";
         } else {
-            std::cerr << "Using conventional NJ\n";
+            std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
             if (numSequences >= 40000)
                 std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
             auto t0 = std::chrono::high_resolution_clock::now();
@@ -750,6 +769,9 @@ int main(int argc, char** argv)
         const int numSequences = matrixReader.numSequences;
         if (numSequences < 3) die("ERROR: need at least three taxa in " + inputFile);
         const int mode = pick_mode(numSequences);
+        if (bionj && mode != 2)
+            die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (mode == 3) { std::cerr << "Divide-and-conquer mode not supported with input matrix\n"; return 1; }
         if (multi) startRanks(ranks, device);
         auto output_ = open_out();
@@ -763,7 +785,7 @@ int main(int argc, char** argv)
             kplacementDeviceArrays.findPlacementTree(dev, params);
             kplacementDeviceArrays.printTree(matrixReader.name, *output_);
         } else {
-            std::cerr << "Using conventional NJ\n";
+            std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
             if (numSequences >= 40000)
                 std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
             NJDeviceArrays njDeviceArrays;

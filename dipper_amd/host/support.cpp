@@ -1,4 +1,5 @@
-// Bootstrap support of the NJ tree of aligned sequences (`--bootstrap N`; no reference counterpart).
+// Bootstrap support of the NJ tree of aligned sequences (`--bootstrap N`; no reference counterpart).  With --bionj the main tree
+// and every replicate tree are BIONJ trees: the contexts carry the variant, everything here consumes merge logs only.
 //
 // The main tree is built exactly as without the option.  Then every rank runs its replicates r = rank, rank + world, .. with
 // no collective: dpr_msa_resample (replicate alignment, on the device) -> dpr_dist_matrix -> dpr_nj_run -> dpr_split_support
@@ -150,6 +151,8 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
         dpr_ctx* c = nullptr;
         if (int rc = dpr_create(&c, ri.device)) fail(ri.rank, "dpr_create (rank-local context)", rc);
         rctx = c;
+        if (bionjOption())
+            if (int rc = dpr_ctx_set_nj_variant(rctx, 1)) fail(ri.rank, "dpr_ctx_set_nj_variant (rank-local context)", rc);
         if (int rc = dpr_set_msa(rctx, packed4, n, seqLen)) fail(ri.rank, "dpr_set_msa (rank-local context)", rc);
     }
     std::vector<int32_t> rx((size_t)k), ry((size_t)k);

@@ -271,6 +271,43 @@ int dpr_get_nj_exchange_info(dpr_ctx *ctx, int *active_plan, int64_t *launches, 
 /* bound of one mailbox / barrier poll in ms (default 2000): a rank whose record does not arrive ends the run with DPR_ERR_COMM */
 int dpr_ctx_set_poll_limit_ms(dpr_ctx *ctx, int ms);
 int dpr_ctx_set_nj_virtual_shards(dpr_ctx *ctx, int w);
+/* Tree-building algorithm of a context: variant 0 = NJ (Saitou & Nei; default), 1 = BIONJ (Gascuel 1997: NJ's pair selection
+ * and branch lengths; the new node's distances are a variance-weighted mean with one weight lambda per merge).  Takes effect
+ * at the context's next dpr_dist_matrix / dpr_reserve_nj.  A BIONJ context always runs the single-rank streaming plan (one
+ * full Q scan per iteration) whatever dpr_set_nj_mode, DPR_NJ_MODE, the adaptive switch and the multi-rank plans say; with
+ * several real ranks every rank builds the whole tree on its own copy of the matrix, no collective.  A context of virtual
+ * ranks (dpr_create_virtual) or with dpr_set_nj_virtual_shards > 1 gets DPR_ERR_ARG from dpr_dist_matrix.  dpr_nj_run is
+ * unchanged: merge log, partial runs and resuming as for NJ.
+ *
+ * Arithmetic contract of BIONJ (fp64, exactly this order of operations, no contraction; the device loop and
+ * dpr_nj_variant_host below produce the same bits):
+ *   State: as the streaming NJ, in slot space -- D, U, Ur and the keys -- plus V with D's layout and row stride, a copy of D
+ *     (pads included) once the distance source has filled D.
+ *   Selection: the Q scan and the reduction of its records, tie-break key and the no-candidate rule q == 10000.0 as for NJ.
+ *   Winner x < y, d = D[y][x], last slot n - 1, r = (double)(n - 2).
+ *   bx0 = (d + U[x]/r - U[y]/r) * 0.5;  by0 = d - bx0.  The merge log receives the clamped lengths exactly as for NJ; the
+ *     update uses the unclamped bx0, by0.
+ *   vxy = V[y][x];  s = sum over the slots k < n of t_k, t_k = V[y][k] - V[x][k] for k != x, y and 0.0 for k = x, y, in the
+ *     canonical order of U[x]: pairwise tree over each chunk of 256 slots, then the chunk partials folded by 256 classes
+ *     (ascending) and combined by the same tree.
+ *   lam = 0.5 + s / (2.0 * r * vxy);  vxy == 0.0 or lam != lam: lam = 0.5;  otherwise clamped to [0.0, 1.0].
+ *   For every slot i < n, i not x or y:
+ *     a = D[x][i] - bx0;  b = D[y][i] - by0;  val = b + lam * (a - b);
+ *     vnew = V[y][i] + lam * (V[x][i] - V[y][i]) - (lam * (1.0 - lam)) * vxy;
+ *     U[i] = U[i] + (-D[x][i] - D[y][i] + val).
+ *   Slot moves as for NJ: the new node takes slot x (row and column: val in D, vnew in V), slot n - 1 moves to y (V moves
+ *   exactly as D does); U[x] = canonical sum of the chunk partials of val. */
+int dpr_ctx_set_nj_variant(dpr_ctx *ctx, int variant);
+/* lambda of the iterations done since the last dpr_dist_matrix of a BIONJ context: out[0 .. *count), *count <= n_total - 2 */
+int dpr_get_nj_lambda(dpr_ctx *ctx, double *out /* n_total-2 */, int64_t *count);
+/* Host-only restatement of the whole loop under the contract above (no GPU; the reference of the tests): selection with
+ * dpr_nj_key, the canonical initial row sums, the update.  variant 0: NJ's val = (dxi + dyi - d) * 0.5 (no V, no lambda).
+ * lower_rows: the strict lower triangle row by row (row i has i entries), as dpr_set_matrix_lower takes it.  Returns the
+ * iterations done: min(n - 2, max_iters) (max_iters < 0: all), fewer when an iteration finds no candidate (the loop ends
+ * there; the log up to it is valid), or DPR_ERR_ARG.  last_d is written when two slots remain.  lambda may be NULL. */
+int64_t dpr_nj_variant_host(int variant, const double *lower_rows, int64_t n, int64_t max_iters,
+                            int32_t *merge_x, int32_t *merge_y, double *bl_x, double *bl_y,
+                            double *last_d, double *lambda /* may be NULL */);
 /* Measurement aid of the pruned NJ loop (bench.py's `timed_kernels` record): stride > 0 makes the following dpr_nj_run
  * calls enqueue their iterations eagerly (no hipGraph replay) with HIP events on the library's stream around the launches
  * of every stride-th iteration; dpr_get_nj_kernel_timing returns the kernels per iteration, the average microseconds per
