@@ -143,6 +143,7 @@ def load_library():
     L.dpr_ctx_set_place_fixed_batch.argtypes = [C.c_void_p, C.c_int64]
     L.dpr_get_place_fixed_timing.argtypes = [C.c_void_p, c_f64p, c_f64p]
     L.dpr_njp_unit_owner.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    L.dpr_nj_plan_resolve.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint64]
     L.dpr_dc_query_share.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dpr_dc_deal_clusters.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int, c_i32p]
     L.dpr_get_dc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), c_f64p]
@@ -234,6 +235,17 @@ def _chk(L, rc):
     if rc < 0:
         raise DipperError(rc, (L.dpr_last_error() or b"").decode())
     return rc
+
+
+(NJ_PLAN_SINGLE_STREAM, NJ_PLAN_SINGLE_PRUNED, NJ_PLAN_BIONJ, NJ_PLAN_ROWS_STREAM, NJ_PLAN_REPLICAS, NJ_PLAN_UNIT_SHARDED,
+ NJ_PLAN_ROWS_PRUNED) = range(7)
+
+
+def nj_plan_resolve(world, virtual_ranks, variant, pruned, multi_plan, virtual_shards, n, total_bytes):
+    """the NJ plan (NJ_PLAN_*) that dist_matrix sets up for n tips under these knobs on a device of total_bytes (host only);
+    raises DipperError where dist_matrix would refuse"""
+    L = load_library()
+    return _chk(L, L.dpr_nj_plan_resolve(world, int(virtual_ranks), variant, int(pruned), multi_plan, virtual_shards, n, total_bytes))
 
 
 def _p(a, t):

@@ -442,31 +442,24 @@ int dpr_get_matrix_row(dpr_ctx* c, int64_t i, double* out)
 {
     if (!c || !c->have_matrix || !out || i < 0 || i >= c->nj[0].N) { set_error("dpr_get_matrix_row: bad argument"); return DPR_ERR_ARG; }
     DPR_HIP(hipStreamSynchronize(c->stream));   // the plain copies below run on the null stream, which does not wait for c->stream
-    if (c->nj[0].pr.in_positions()) {
-        // position space: row of slot i, columns gathered through pos_of_slot (dead slots read +inf)
-        NjPruned& q = c->nj[0].pr;
-        const int64_t N = c->nj[0].N;
-        std::vector<int32_t> pos((size_t)N);
-        std::vector<double> row((size_t)q.P);
-        DPR_HIP(hipMemcpy(pos.data(), q.pos_of_slot, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
-        if (pos[(size_t)i] >= 0 && pos[(size_t)i] < q.P) {
-            const double* src = q.D + (int64_t)pos[(size_t)i] * q.ld;
-            if (c->nj_row_pruned) {      // rows sharded: the owner's epoch buffer as mapped here
-                const NjRowShard& rs = c->nj[0].rs;
-                src = rs.peer_half[(q.epoch_index + 1) & 1][(size_t)njr_owner(pos[(size_t)i], c->world)] + njr_local_row(pos[(size_t)i], c->world) * q.ld;
-            }
-            DPR_HIP(hipMemcpy(row.data(), src, sizeof(double) * (size_t)q.P, hipMemcpyDeviceToHost));
-        }
-        if (pos[(size_t)i] < 0 || pos[(size_t)i] >= q.P) {      // slot not alive any more
-            for (int64_t j = 0; j < N; ++j) out[j] = __builtin_inf();
-            return DPR_OK;
-        }
-        for (int64_t j = 0; j < N; ++j) out[j] = (pos[(size_t)j] >= 0 && pos[(size_t)j] < q.P) ? row[(size_t)pos[(size_t)j]] : __builtin_inf();
+    const NjPruned& q = c->nj[0].pr;
+    const int64_t N = c->nj[0].N;
+    if (!q.in_positions()) {
+        const double* src = slot_row(c, i, 0, false);
+        if (!src) { set_error("dpr_get_matrix_row: row not owned by this rank"); return DPR_ERR_ARG; }
+        DPR_HIP(hipMemcpy(out, src, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
         return DPR_OK;
     }
-    NjBuffers* b = owner_buffers(c, i);
-    if (!b) { set_error("dpr_get_matrix_row: row not owned by this rank"); return DPR_ERR_ARG; }
-    DPR_HIP(hipMemcpy(out, b->D + shard_local_row(i, c->world) * b->ld, sizeof(double) * (size_t)b->N, hipMemcpyDeviceToHost));
+    // position space: row of slot i, columns gathered through pos_of_slot (dead slots read +inf)
+    std::vector<int32_t> pos((size_t)N);
+    std::vector<double> row((size_t)q.P);
+    DPR_HIP(hipMemcpy(pos.data(), q.pos_of_slot, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    if (pos[(size_t)i] < 0 || pos[(size_t)i] >= q.P) {      // slot not alive any more
+        for (int64_t j = 0; j < N; ++j) out[j] = __builtin_inf();
+        return DPR_OK;
+    }
+    DPR_HIP(hipMemcpy(row.data(), slot_row(c, i, pos[(size_t)i], false), sizeof(double) * (size_t)q.P, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < N; ++j) out[j] = (pos[(size_t)j] >= 0 && pos[(size_t)j] < q.P) ? row[(size_t)pos[(size_t)j]] : __builtin_inf();
     return DPR_OK;
 }
 

@@ -62,7 +62,7 @@ int njr_gather_cb(void* ctx, int kind, hipStream_t s)
 
 int exchange(dpr_ctx* c, ExKind kind)
 {
-    if (c->world == 1 || c->nj_replicated) return DPR_OK;
+    if (c->plan.whole_matrix()) return DPR_OK;
     if (c->vworld > 0) {
         for (int r = 0; r < c->vworld; ++r) {
             NjBuffers& src = c->nj[(size_t)r];
@@ -178,15 +178,14 @@ int rccl_gather_bytes(dpr_ctx* c, const void* mine, void* all, size_t bytes)
 // Set up the exchange plan of the row-sharded loop for the buffers nj_alloc just provided.  A plan that cannot be set up
 // on EVERY rank (no fine-grained window, IPC handles refused, a mapping fails) falls back to the legacy loop on all
 // ranks together -- the decision is taken on gathered flags, so the ranks cannot disagree -- and says why in
-// nj_exchange_note.  Ranks joined without RCCL (dpr_comm_init_local) have nothing to fall back to: error.
+// nj_exchange_note; what came of it is c->plan.exchange (kNjsLegacy on entry: dpr_dist_matrix).  Ranks joined without RCCL
+// (dpr_comm_init_local) have nothing to fall back to: error.
 // force_windows (row-sharded pruned NJ): windows and peer mappings are needed whatever the streaming loop's plan is -- the
 // epoch builds pull rows from the peers' buffers, the mailbox plan exchanges through the windows
 int njs_setup(dpr_ctx* c, bool force_windows)
 {
     int plan = ctx_exchange_plan(c);
     if (force_windows && plan == kNjsLegacy) plan = (c->comm && c->vworld == 0) ? kNjsPeer : kNjsMailbox;
-    c->nj_exchange_active = kNjsLegacy;
-    c->nj_exchange_note.clear();
     c->njs_pending = false;
     if (plan == kNjsLegacy) return DPR_OK;
     if (c->world > kNjsMaxWorld) { c->nj_exchange_note = "more ranks than mailbox slots"; return DPR_OK; }
@@ -202,14 +201,14 @@ int njs_setup(dpr_ctx* c, bool force_windows)
         for (int r = 0; r < c->vworld; ++r) { wins[(size_t)r] = c->nj[(size_t)r].peer.win; Ds[(size_t)r] = c->nj[(size_t)r].D; }
         for (auto& b : c->nj)
             if (int rc = njs_set_peers(b, wins.data(), Ds.data(), c->stream)) return rc;
-        c->nj_exchange_active = plan;
+        c->plan.exchange = plan;
         return DPR_OK;
     }
     NjBuffers& b = c->nj[0];
     if (c->local_comm && !c->shm) {       // (ranks joined through a shared region exchange their handles themselves, below)
         if (!ok) return DPR_ERR_HIP;
         if (!b.peer.attached) { set_error("dpr_dist_matrix: ranks joined by dpr_comm_init_local need dpr_peer_export / dpr_peer_attach for this tip count first"); return DPR_ERR_STATE; }
-        c->nj_exchange_active = kNjsMailbox;
+        c->plan.exchange = kNjsMailbox;
         return DPR_OK;
     }
     // attach or skip: decided on GATHERED flags, never on this rank's own state -- if one rank's buffers were recreated
@@ -255,16 +254,16 @@ int njs_setup(dpr_ctx* c, bool force_windows)
             return DPR_OK;
         }
     }
-    c->nj_exchange_active = plan;
+    c->plan.exchange = plan;
     return DPR_OK;
 }
 
-// barrier over the ranks of the sharded loop, enqueued on the context's stream
+// barrier over the ranks of a rows-dealt plan whose windows are set up (plan.exchange is not the legacy one), enqueued on the
+// context's stream
 int njs_barrier(dpr_ctx* c)
 {
-    if (c->vworld > 0 || c->world == 1) return DPR_OK;       // one stream: already ordered
+    if (c->vworld > 0) return DPR_OK;                        // one stream: already ordered
     if (c->comm) return exchange(c, EX_RECS);                // (the gathered records are dead between iterations)
-    if (c->shm && c->nj_exchange_active == kNjsLegacy) return comm_barrier(c, c->stream);      // (no peer windows were set up)
     return njs_launch_barrier(c->nj[0], c->stream);
 }
 
@@ -273,13 +272,6 @@ int njr_barrier_cb(void* ctx)
 {
     dpr_ctx* c = static_cast<dpr_ctx*>(ctx);
     return comm_barrier(c, c->stream);
-}
-
-NjBuffers* owner_buffers(dpr_ctx* c, int64_t row)
-{
-    const int o = shard_owner(row, c->world);
-    if (c->vworld > 0) return &c->nj[(size_t)o];
-    return o == c->rank ? &c->nj[0] : nullptr;
 }
 
 }  // namespace dpr
@@ -332,9 +324,11 @@ int dpr_peer_export(dpr_ctx* c, int64_t n_tips, void* out192)
     if (!c || !out192 || n_tips < 2 || n_tips >= (1 << 24)) { set_error("dpr_peer_export: bad argument"); return DPR_ERR_ARG; }
     if (c->world < 2 || c->vworld > 0) { set_error("dpr_peer_export: needs a multi-rank context"); return DPR_ERR_STATE; }
     DPR_HIP(hipSetDevice(c->device));
+    const int kind = ctx_nj_plan(c, n_tips, "dpr_peer_export");
+    if (kind < 0) return kind;
     c->have_matrix = 0;
     NjBuffers& b = c->nj[0];
-    if (int rc = nj_alloc(b, n_tips, c->rank, c->world, c->stream, ctx_njr(c, n_tips) ? njr_twin_rows(n_tips, c->world) : 0)) return rc;
+    if (int rc = nj_alloc(b, n_tips, c->rank, c->world, c->stream, kind == DPR_NJ_PLAN_ROWS_PRUNED ? njr_twin_rows(n_tips, c->world) : 0)) return rc;
     b.peer.plan = kNjsMailbox;
     if (int rc = njs_alloc_window(b, c->stream)) return rc;
     --b.peer.run_id;          // (dpr_dist_matrix's own njs_alloc_window call counts the run)
@@ -379,7 +373,7 @@ int dpr_ctx_set_nj_exchange(dpr_ctx* c, int plan)
 int dpr_get_nj_exchange_info(dpr_ctx* c, int* active_plan, int64_t* launches, int64_t* collectives, char* note, int cap)
 {
     if (!c) { set_error("dpr_get_nj_exchange_info: null ctx"); return DPR_ERR_ARG; }
-    if (active_plan) *active_plan = c->nj_exchange_active;
+    if (active_plan) *active_plan = c->plan.exchange;
     if (launches) *launches = c->nj_launches;
     if (collectives) *collectives = c->nj_collectives;
     if (note && cap > 0) std::snprintf(note, (size_t)cap, "%s", c->nj_exchange_note.c_str());
@@ -395,7 +389,7 @@ int dpr_ctx_set_debug_fault(dpr_ctx* c, int64_t iteration, int rank)
     for (auto& b : c->nj) {
         b.peer.fault_it = iteration; b.peer.fault_rank = rank;
         // (a captured graph of the row-sharded pruned loop holds its arguments by value: capture again with the new setting)
-        if (c->nj_row_pruned && b.pr.graph) { (void)hipGraphExecDestroy(b.pr.graph); b.pr.graph = nullptr; }
+        if (c->plan.kind == DPR_NJ_PLAN_ROWS_PRUNED && b.pr.graph) { (void)hipGraphExecDestroy(b.pr.graph); b.pr.graph = nullptr; }
     }
     return DPR_OK;
 }
@@ -405,7 +399,7 @@ int dpr_ctx_set_poll_limit_ms(dpr_ctx* c, int ms)
     if (!c || ms < 1) { set_error("dpr_ctx_set_poll_limit_ms: ms >= 1"); return DPR_ERR_ARG; }
     for (auto& b : c->nj) {
         b.peer.poll_ticks = (unsigned long long)ms * 100000ull;
-        if (c->nj_row_pruned && b.pr.graph) { (void)hipGraphExecDestroy(b.pr.graph); b.pr.graph = nullptr; }
+        if (c->plan.kind == DPR_NJ_PLAN_ROWS_PRUNED && b.pr.graph) { (void)hipGraphExecDestroy(b.pr.graph); b.pr.graph = nullptr; }
     }
     return DPR_OK;
 }

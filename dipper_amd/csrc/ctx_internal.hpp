@@ -29,6 +29,18 @@ extern Rccl g_rccl;
 int rccl_load();
 const std::string& last_error();
 struct ShmComm;                     // ranks joined through a shared host region (ctx_shm.hip)
+
+// How a context builds its NJ tree.  dpr_nj_plan_resolve is the only place that chooses a kind; dpr_dist_matrix stores it and
+// every later entry point reads it, through the predicates where several kinds share an answer.
+struct NjPlan {
+    int kind = DPR_NJ_PLAN_SINGLE_STREAM;      // DPR_NJ_PLAN_* (include/dipper_hip.h)
+    // the two rows-dealt kinds: exchange plan that njs_setup got going (a set-up that fails on some rank falls back to the legacy
+    // loop on all of them and says why in nj_exchange_note); kNjsLegacy for every other kind
+    int exchange = kNjsLegacy;
+    bool rows_dealt() const { return kind == DPR_NJ_PLAN_ROWS_STREAM || kind == DPR_NJ_PLAN_ROWS_PRUNED; }   // a rank holds only its share of the rows
+    bool whole_matrix() const { return !rows_dealt(); }      // every rank holds the whole matrix: allocated as rank 0 of 1, nothing to exchange
+    bool one_exchange_loop() const { return kind == DPR_NJ_PLAN_ROWS_STREAM && exchange != kNjsLegacy; }     // njs.hip's loop, not nj.hip's
+};
 }  // namespace dpr
 
 struct dpr_ctx {
@@ -54,9 +66,7 @@ struct dpr_ctx {
     double* packed_lower = nullptr;  // MATRIX source, device
     int64_t n_input = 0;
     int have_matrix = 0;
-    bool nj_replicated = false;      // several ranks, each holding the whole matrix (pruned NJ)
-    bool nj_unit_sharded = false;    // ... and sharing the unit tests / scans of an iteration (else: every rank runs the single-GPU plan)
-    bool nj_row_pruned = false;      // several ranks, rows sharded, exact pruned NJ (njr.hip)
+    dpr::NjPlan plan;                // what the last dpr_dist_matrix set up
     double dist_ms = 0, nj_ms = 0;
     double place_dist_ms = 0;        // distance rows of the last placement run (the rest of nj_ms is tree work)
     std::vector<hipEvent_t> place_ev;   // event pairs whose sum is the reported distance part of the current placement run
@@ -70,12 +80,10 @@ struct dpr_ctx {
     // plan knobs of THIS context (dpr_ctx_set_*); -1 = follow the process-wide default (dpr_set_* / environment)
     int nj_mode = -1, nj_vshards = -1, nj_multi_plan = -1;
     int nj_variant = 0;              // dpr_ctx_set_nj_variant: 0 NJ, 1 BIONJ; read by the next dpr_dist_matrix / dpr_reserve_nj
-    bool nj_bionj = false;           // the matrix of the last dpr_dist_matrix was set up for BIONJ (single-rank streaming plan, V beside D)
     int nj_adaptive = -1;            // adaptive pruned / streaming plan of the single-rank NJ (-1 = DPR_NJ_ADAPTIVE, default on)
-    // row-sharded streaming NJ: exchange plan of the loop (-1 = DPR_NJ_EXCHANGE, default peer; see njs.hip) and what the
-    // last dpr_dist_matrix actually set up (a failed peer set-up falls back to the legacy loop and says why)
+    // row-sharded streaming NJ: exchange plan asked for (-1 = DPR_NJ_EXCHANGE, default peer; see njs.hip); what came of it is
+    // plan.exchange, and in words the note (cleared at the start of every dpr_dist_matrix)
     int nj_exchange = -1;
-    int nj_exchange_active = dpr::kNjsLegacy;
     std::string nj_exchange_note;
     bool local_comm = false;         // ranks joined by dpr_comm_init_local: no RCCL, windows attached by the launcher
     bool njs_pending = false;        // the rows of the last merge still live in the row buffers
@@ -91,7 +99,8 @@ bool want_pruned(const dpr_ctx* c);
 int ctx_exchange_plan(const dpr_ctx* c);
 int ctx_multi_plan(const dpr_ctx* c);
 int ctx_vshards(const dpr_ctx* c);
-bool ctx_njr(const dpr_ctx* c, int64_t n);
+int ctx_nj_plan(dpr_ctx* c, int64_t n, const char* who);      // kind for n tips under the context's knobs as they stand, or an error in who's name
+const double* slot_row(dpr_ctx* c, int64_t slot, int64_t pos, bool peer_matrix);
 int64_t njr_twin_rows(int64_t n, int world);
 int fetch_state(dpr_ctx* c, NjState* st);
 // ctx_comm.hip: exchanges, peer windows, barriers
@@ -101,7 +110,6 @@ int njs_barrier(dpr_ctx* c);
 int njr_barrier_cb(void* ctx);
 int njr_gather_cb(void* ctx, int kind, hipStream_t s);
 int njp_gather_cb(void* ctx, void* buf, size_t bytes_per_rank, hipStream_t s);
-NjBuffers* owner_buffers(dpr_ctx* c, int64_t row);
 int rccl_gather_bytes(dpr_ctx* c, const void* mine, void* all, size_t bytes);
 // ctx_shm.hip: the transport-independent collectives the algorithms call (RCCL communicator, or the device windows of ranks
 // joined through a shared host region)

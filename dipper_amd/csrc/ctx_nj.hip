@@ -1,6 +1,6 @@
-// C ABI, distance matrix and neighbor joining: plan selection (single GPU: pruned / streaming; several ranks: replicated,
-// unit-sharded, row-sharded streaming, row-sharded pruned), dpr_dist_matrix, dpr_nj_run, dpr_argmin_once and the NJ getters.
-// BIONJ (dpr_ctx_set_nj_variant): always the single-rank streaming plan; dpr_nj_variant_host restates the streaming loop on the host.
+// C ABI, distance matrix and neighbor joining: plan selection (dpr_nj_plan_resolve: the only place that chooses among the seven
+// DPR_NJ_PLAN_* kinds), dpr_dist_matrix, dpr_nj_run, dpr_argmin_once and the NJ getters.
+// BIONJ (dpr_ctx_set_nj_variant): always the streaming loop on the rank's own copy; dpr_nj_variant_host restates that loop on the host.
 #include "ctx_internal.hpp"
 
 namespace dpr {
@@ -48,19 +48,17 @@ int ctx_exchange_plan(const dpr_ctx* c)
 int ctx_multi_plan(const dpr_ctx* c) { return c->nj_multi_plan >= 0 ? c->nj_multi_plan : nj_multi_plan(); }
 int ctx_vshards(const dpr_ctx* c) { return c->nj_vshards >= 1 ? c->nj_vshards : g_nj_vshards; }
 
-// Row-sharded exact pruned NJ (njr.hip): asked for (plan 3; the only way for a context of virtual ranks), or -- real ranks,
-// plan auto -- when the two epoch buffers of the replicated plans (2 x 8 n^2 bytes) no longer fit this device
-bool ctx_njr(const dpr_ctx* c, int64_t n)
+// The plan this context sets up for n tips: its knobs as they stand now, and the device's memory where the resolver can ask for it
+// (the auto rule of real ranks).  kind, or the resolver's error with the caller's name in front
+int ctx_nj_plan(dpr_ctx* c, int64_t n, const char* who)
 {
-    if (c->world < 2 || n < 3 || !want_pruned(c)) return false;
-    const int plan = ctx_multi_plan(c);
-    if (plan == 3) return true;
-    if (plan != 0 || c->vworld > 0) return false;
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return 2.0 * 8.0 * (double)n * (double)n > 0.85 * (double)total_b;
+    if (c->world > 1 && c->vworld == 0 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); total_b = ~(size_t)0; }   // (unknown: never too small)
+    const int kind = dpr_nj_plan_resolve(c->world, c->vworld > 0, c->nj_variant, want_pruned(c), ctx_multi_plan(c), ctx_vshards(c), n, total_b);
+    if (kind < 0) set_error(std::string(who) + ": " + last_error());
+    return kind;
 }
-// matrix rows per epoch buffer of a rank under that plan: the same on every rank (the peers compute each other's second half)
+// matrix rows per epoch buffer of a rank under the rows-pruned plan: the same on every rank (the peers compute each other's second half)
 int64_t njr_twin_rows(int64_t n, int world)
 {
     const int64_t nblk = (n + kRowBlock - 1) / kRowBlock;
@@ -73,27 +71,50 @@ static std::vector<NjBuffers*> njr_ranks(dpr_ctx* c)
     for (auto& b : c->nj) v.push_back(&b);
     return v;
 }
-// one NJ iteration (active size n, iteration index it) on every rank held by this context
+// Where the matrix row of slot `slot` can be read from this process (position space: `pos` is the slot's position, and the row's
+// columns are positions); nullptr: another real rank holds it and no mapping of it exists here.  peer_matrix: the row may be read
+// through the mapping of a peer's slot-space matrix -- for a caller that knows the peers' flushes are behind a barrier.
+const double* slot_row(dpr_ctx* c, int64_t slot, int64_t pos, bool peer_matrix)
+{
+    NjBuffers& b0 = c->nj[0];
+    const NjPruned& q = b0.pr;
+    if (q.in_positions()) {
+        if (c->plan.kind != DPR_NJ_PLAN_ROWS_PRUNED) return q.D + pos * q.ld;
+        // rows dealt by position: the owner's epoch buffer of the moment, as mapped here
+        return b0.rs.peer_half[(q.epoch_index + 1) & 1][(size_t)njr_owner(pos, c->world)] + njr_local_row(pos, c->world) * q.ld;
+    }
+    if (c->plan.whole_matrix()) return b0.D + slot * b0.ld;
+    const int o = shard_owner(slot, c->world);
+    const int64_t off = shard_local_row(slot, c->world) * b0.ld;
+    if (c->vworld > 0) return c->nj[(size_t)o].D + off;
+    if (o == c->rank) return b0.D + off;
+    return peer_matrix && c->plan.exchange != kNjsLegacy && !b0.peer.h_D.empty() ? b0.peer.h_D[(size_t)o] + off : nullptr;
+}
+// one NJ iteration (active size n, iteration index it) of the eager streaming loops, on every rank held by this context
 static int nj_iteration(dpr_ctx* c, int64_t n, int64_t it)
 {
-    if (c->nj_bionj) {
-        // BIONJ: this rank's own copy whatever the world; the lambda kernel reads the rows of V that the update rewrites
-        NjBuffers& b = c->nj[0];
-        if (int rc = nj_launch_scan(b, false, n, it, c->stream)) return rc;
-        if (int rc = nj_launch_bionj_lambda(b, n, c->stream)) return rc;
+    NjBuffers& b0 = c->nj[0];
+    switch (c->plan.kind) {
+    case DPR_NJ_PLAN_BIONJ:
+        // this rank's own copy whatever the world; the lambda kernel reads the rows of V that the update rewrites
+        if (int rc = nj_launch_scan(b0, false, n, it, c->stream)) return rc;
+        if (int rc = nj_launch_bionj_lambda(b0, n, c->stream)) return rc;
         c->nj_launches += 3;
-        return nj_launch_bionj_post(b, n, it, c->stream);
+        return nj_launch_bionj_post(b0, n, it, c->stream);
+    case DPR_NJ_PLAN_SINGLE_STREAM:
+        if (int rc = nj_launch_scan(b0, false, n, it, c->stream)) return rc;
+        return nj_launch_post(b0, n, it, c->stream);
+    case DPR_NJ_PLAN_ROWS_STREAM:
+        break;
+    default:
+        set_error("dpr_nj_run: internal: the pruned plans have loops of their own");
+        return DPR_ERR_STATE;
     }
-    if (c->world == 1) {
-        NjBuffers& b = c->nj[0];
-        if (int rc = nj_launch_scan(b, false, n, it, c->stream)) return rc;
-        return nj_launch_post(b, n, it, c->stream);
-    }
-    if (c->nj_exchange_active != kNjsLegacy) {
+    if (c->plan.one_exchange_loop()) {
         // one exchange, two launches (njs.hip): scan + record, [all-gather of the records | nothing: mailboxes], update
         for (auto& b : c->nj)
             if (int rc = njs_launch_scan(b, n, it, c->njs_pending, c->stream)) return rc;
-        if (c->nj_exchange_active == kNjsPeer)
+        if (c->plan.exchange == kNjsPeer)
             if (int rc = exchange(c, EX_RECS64)) return rc;
         for (auto& b : c->nj)
             if (int rc = njs_launch_post(b, n, it, c->njs_pending, c->stream)) return rc;
@@ -114,6 +135,103 @@ static int nj_iteration(dpr_ctx* c, int64_t n, int64_t it)
         if (int rc = nj_launch_update_sharded(b, n, c->stream)) return rc;
     return DPR_OK;
 }
+
+// ---- the steps of dpr_dist_matrix behind the source check and the resolver; each reads c->plan ------------------------------------
+// the buffers of every rank held here; dealt rows also get their exchange set up (windows, peer mappings)
+static int dist_alloc(dpr_ctx* c, int64_t n)
+{
+    // a whole copy (7.2 GB at 30 000 tips, 80 GB at 100 000) is allocated as rank 0 of 1, whatever the world
+    const bool whole = c->plan.whole_matrix(), njr = c->plan.kind == DPR_NJ_PLAN_ROWS_PRUNED;
+    for (size_t r = 0; r < c->nj.size(); ++r)
+        if (int rc = nj_alloc(c->nj[r], n, whole ? 0 : (c->vworld > 0 ? (int)r : c->rank), whole ? 1 : c->world, c->stream, njr ? njr_twin_rows(n, c->world) : 0,
+                              c->plan.kind == DPR_NJ_PLAN_BIONJ)) return rc;
+    if (!c->plan.rows_dealt()) return DPR_OK;
+    if (int rc = njs_setup(c, njr)) return rc;
+    if (njr && c->plan.exchange == kNjsLegacy) {
+        set_error("dpr_dist_matrix: the row-sharded pruned NJ needs the peers' buffers mapped on every rank (" + c->nj_exchange_note + "); use DPR_NJ_MODE=stream");
+        return DPR_ERR_STATE;
+    }
+    return DPR_OK;
+}
+static int dist_fill(dpr_ctx* c, int source, int dist_type, int64_t n)
+{
+    for (auto& b : c->nj) {
+        if (source == DPR_SRC_MSA) {
+            if (int rc = msa_dist_rows(c->msa, b, dist_type, c->stream)) return rc;
+        } else if (source == DPR_SRC_MASH) {
+            if (b.world > 1) {
+                if (int rc = mash_dist_matrix_sharded(c->mash, b.rank, b.world, b.rows_local, b.D, b.ld, c->stream)) return rc;
+            } else {
+                for (int64_t r0 = 0; r0 < b.rows_local; r0 += 32768) {
+                    const int64_t nr = b.rows_local - r0 < 32768 ? b.rows_local - r0 : 32768;
+                    if (int rc = mash_dist_rows(c->mash, r0, nr, b.rank, b.world, true, n, b.D + r0 * b.ld, b.ld, c->stream)) return rc;
+                }
+            }
+        } else {
+            if (int rc = nj_expand_lower(b, c->packed_lower, c->stream)) return rc;
+        }
+        if (c->plan.kind == DPR_NJ_PLAN_BIONJ)
+            if (int rc = nj_bionj_init(b, c->stream)) return rc;
+    }
+    return DPR_OK;
+}
+// row sums of the own rows: into U (whole matrix here), the slice of the legacy exchange, or the window's slice (windows set up:
+// every rank then reads the other ranks' sums straight from their windows, behind one barrier); then Ur and the keys
+static int dist_row_sums(dpr_ctx* c)
+{
+    const bool dealt = c->plan.rows_dealt(), windows = dealt && c->plan.exchange != kNjsLegacy;
+    for (auto& b : c->nj)
+        if (int rc = nj_init_sums(b, c->stream, !dealt ? nullptr : windows ? reinterpret_cast<double*>(b.peer.win + b.peer.lay.off_slice) : b.slice)) return rc;
+    if (dealt)
+        if (int rc = windows ? njs_barrier(c) : exchange(c, EX_U)) return rc;
+    for (auto& b : c->nj) {
+        if (dealt)
+            if (int rc = windows ? njs_launch_unpack_u(b, c->stream) : nj_launch_unpack_u(b, c->stream)) return rc;
+        if (int rc = nj_prepare(b, c->stream)) return rc;
+    }
+    return DPR_OK;
+}
+// rows-pruned plan: the epoch state of njr.hip on every rank held here
+static int dist_build_njr(dpr_ctx* c)
+{
+    // exchange plan of the loop: -1 / 0 = default (collective -- all-gathers -- with RCCL and between virtual ranks; mailbox for
+    // ranks joined without RCCL), 1 = collective, 2 = mailbox
+    int rplan = c->nj_exchange == 2 ? kNjrMailbox : c->nj_exchange == 1 ? kNjrCollective : (c->local_comm ? kNjrMailbox : kNjrCollective);
+    if (c->nj_exchange < 0 && !c->local_comm)
+        if (const char* e = std::getenv("DPR_NJ_EXCHANGE")) rplan = std::strcmp(e, "mailbox") == 0 ? kNjrMailbox : kNjrCollective;
+    if (rplan == kNjrCollective && c->vworld == 0 && !comm_real(c)) { set_error("dpr_dist_matrix: the collective plan of the row-sharded pruned NJ needs a transport between the ranks (RCCL, or dpr_comm_init_shared)"); return DPR_ERR_STATE; }
+    for (auto& b : c->nj) {
+        b.rs.world = c->world; b.rs.rank = b.rank; b.rs.plan = rplan;
+        b.rs.win_off = b.peer.lay.off_njr;
+        b.rs.gather = njr_gather_cb; b.rs.cb_ctx = c;
+        // (ranks on the shared region's windows: with the mailbox plan the barrier runs through the njr windows, no callback;
+        //  with the collective plan through the region)
+        b.rs.barrier = (c->vworld == 0 && (c->comm || (c->shm && rplan == kNjrCollective))) ? njr_barrier_cb : nullptr;
+        b.rs.launches = 0; b.rs.collectives = 0;
+    }
+    std::vector<NjBuffers*> ranks = njr_ranks(c);
+    if (int rc = njr_build(ranks, c->stream)) return rc;
+    c->nj_exchange_note = std::string("row-sharded pruned NJ (njr.hip), exchange plan ") + (rplan == kNjrMailbox ? "mailbox" : "collective");
+    return DPR_OK;
+}
+// the pruned plans on a whole copy: who shares the unit tests and scans of an iteration -- the real ranks (unit-sharded), emulated
+// ones (virtual shards), or nobody
+static void njp_set_shards(dpr_ctx* c, int kind)
+{
+    NjPruned& q = c->nj[0].pr;
+    if (kind == DPR_NJ_PLAN_UNIT_SHARDED) { q.sh_world = c->world; q.sh_rank = c->rank; q.sh_virtual = false; q.gather = njp_gather_cb; q.gather_ctx = c; }
+    else if (ctx_vshards(c) > 1) { q.sh_world = ctx_vshards(c); q.sh_rank = 0; q.sh_virtual = true; }
+}
+static int dist_build_njp(dpr_ctx* c)
+{
+    NjPruned& q = c->nj[0].pr;
+    njp_set_shards(c, c->plan.kind);
+    if (c->nj_adaptive >= 0) q.adaptive = c->nj_adaptive;
+    if (int rc = njp_build(c->nj[0], c->stream)) return rc;
+    if (c->nj_adaptive >= 0) q.adaptive = c->nj_adaptive;      // (the explicit setting wins over the environment)
+    return DPR_OK;
+}
+static bool plan_is_njp(int kind) { return kind == DPR_NJ_PLAN_SINGLE_PRUNED || kind == DPR_NJ_PLAN_REPLICAS || kind == DPR_NJ_PLAN_UNIT_SHARDED; }
 
 }  // namespace dpr
 
@@ -144,100 +262,16 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
         set_error("dpr_dist_matrix: source not available");
         return DPR_ERR_ARG;
     }
-    // BIONJ (dpr_ctx_set_nj_variant): the single-rank streaming plan on this rank's own copy of the matrix, whatever the
-    // NJ mode, the adaptive switch and the multi-rank plans say
-    const bool bionj = c->nj_variant == 1;
-    if (bionj && (c->vworld > 0 || ctx_vshards(c) > 1)) {
-        set_error("dpr_dist_matrix: BIONJ runs the single-rank streaming plan: not on a context of virtual ranks or with virtual shards (dpr_set_nj_virtual_shards > 1)");
-        return DPR_ERR_ARG;
-    }
+    const int kind = ctx_nj_plan(c, n, "dpr_dist_matrix");
+    if (kind < 0) return kind;
     c->have_matrix = 0;
-    c->nj_bionj = bionj;
-    // Several real ranks + pruned NJ: every rank builds and keeps the WHOLE matrix (7.2 GB at 30 000 tips, 80 GB at
-    // 100 000) and the ranks share the per-iteration unit tests and scans (njp.hip, unit-sharded mode).  The
-    // streaming algorithm (DPR_NJ_MODE=stream) keeps the row-sharded layout.
-    const bool njr = !bionj && ctx_njr(c, n);
-    const bool repl = bionj ? c->world > 1 : (!njr && c->world > 1 && c->vworld == 0 && want_pruned(c) && n >= 3);
-    c->nj_replicated = repl;
-    if (bionj) c->nj_unit_sharded = false;
-    c->nj_row_pruned = false;
-    for (size_t r = 0; r < c->nj.size(); ++r)
-        if (int rc = nj_alloc(c->nj[r], n, repl ? 0 : (c->vworld > 0 ? (int)r : c->rank), repl ? 1 : c->world, c->stream, njr ? njr_twin_rows(n, c->world) : 0, bionj)) return rc;
-    const bool row_sharded = c->world > 1 && !repl;
-    if (row_sharded) { if (int rc = njs_setup(c, njr)) return rc; }
-    else c->nj_exchange_active = kNjsLegacy;
-    if (njr && c->nj_exchange_active == kNjsLegacy) {
-        set_error("dpr_dist_matrix: the row-sharded pruned NJ needs the peers' buffers mapped on every rank (" + c->nj_exchange_note + "); use DPR_NJ_MODE=stream");
-        return DPR_ERR_STATE;
-    }
-    const bool peer_plan = row_sharded && c->nj_exchange_active != kNjsLegacy;
+    c->plan = NjPlan{ kind, kNjsLegacy };
+    c->nj_exchange_note.clear();
+    if (int rc = dist_alloc(c, n)) return rc;
     DPR_HIP(hipEventRecord(c->ev[0], c->stream));
-    for (auto& b : c->nj) {
-        if (source == DPR_SRC_MSA) {
-            if (int rc = msa_dist_rows(c->msa, b, dist_type, c->stream)) return rc;
-        } else if (source == DPR_SRC_MASH) {
-            if (b.world > 1) {
-                if (int rc = mash_dist_matrix_sharded(c->mash, b.rank, b.world, b.rows_local, b.D, b.ld, c->stream)) return rc;
-            } else {
-                for (int64_t r0 = 0; r0 < b.rows_local; r0 += 32768) {
-                    const int64_t nr = b.rows_local - r0 < 32768 ? b.rows_local - r0 : 32768;
-                    if (int rc = mash_dist_rows(c->mash, r0, nr, b.rank, b.world, true, n, b.D + r0 * b.ld, b.ld, c->stream)) return rc;
-                }
-            }
-        } else {
-            if (int rc = nj_expand_lower(b, c->packed_lower, c->stream)) return rc;
-        }
-        if (bionj)
-            if (int rc = nj_bionj_init(b, c->stream)) return rc;
-        // row sums of the own rows: into U (one rank), the slice of the legacy exchange, or the window's slice (peer plans)
-        double* sums = !row_sharded ? nullptr : peer_plan ? reinterpret_cast<double*>(b.peer.win + b.peer.lay.off_slice) : b.slice;
-        if (int rc = nj_init_sums(b, c->stream, sums)) return rc;
-    }
-    if (row_sharded && peer_plan) {
-        // every rank reads the other ranks' sums straight from their windows, behind one barrier
-        if (int rc = njs_barrier(c)) return rc;
-        for (auto& b : c->nj)
-            if (int rc = njs_launch_unpack_u(b, c->stream)) return rc;
-    } else if (row_sharded) {
-        if (int rc = exchange(c, EX_U)) return rc;
-        for (auto& b : c->nj)
-            if (int rc = nj_launch_unpack_u(b, c->stream)) return rc;
-    }
-    for (auto& b : c->nj)
-        if (int rc = nj_prepare(b, c->stream)) return rc;
-    if (njr) {
-        // exchange plan of the loop: -1 / 0 = default (collective -- all-gathers -- with RCCL and between virtual ranks; mailbox for
-        // ranks joined without RCCL), 1 = collective, 2 = mailbox
-        int rplan = c->nj_exchange == 2 ? kNjrMailbox : c->nj_exchange == 1 ? kNjrCollective : (c->local_comm ? kNjrMailbox : kNjrCollective);
-        if (c->nj_exchange < 0 && !c->local_comm)
-            if (const char* e = std::getenv("DPR_NJ_EXCHANGE")) rplan = std::strcmp(e, "mailbox") == 0 ? kNjrMailbox : kNjrCollective;
-        if (rplan == kNjrCollective && c->vworld == 0 && !comm_real(c)) { set_error("dpr_dist_matrix: the collective plan of the row-sharded pruned NJ needs a transport between the ranks (RCCL, or dpr_comm_init_shared)"); return DPR_ERR_STATE; }
-        for (size_t r = 0; r < c->nj.size(); ++r) {
-            NjBuffers& b = c->nj[r];
-            b.rs.world = c->world; b.rs.rank = c->vworld > 0 ? (int)r : c->rank; b.rs.plan = rplan;
-            b.rs.win_off = b.peer.lay.off_njr;
-            b.rs.gather = njr_gather_cb; b.rs.cb_ctx = c;
-            // (ranks on the shared region's windows: with the mailbox plan the barrier runs through the njr windows, no callback;
-            //  with the collective plan through the region)
-            b.rs.barrier = (c->vworld == 0 && (c->comm || (c->shm && rplan == kNjrCollective))) ? njr_barrier_cb : nullptr;
-            b.rs.launches = 0; b.rs.collectives = 0;
-        }
-        std::vector<NjBuffers*> ranks = njr_ranks(c);
-        if (int rc = njr_build(ranks, c->stream)) return rc;
-        c->nj_row_pruned = true;
-        c->nj_exchange_note = std::string("row-sharded pruned NJ (njr.hip), exchange plan ") + (rplan == kNjrMailbox ? "mailbox" : "collective");
-    }
-    if (!bionj && (c->world == 1 || repl) && want_pruned(c) && n >= 3) {
-        NjPruned& q = c->nj[0].pr;
-        const int plan = ctx_multi_plan(c);
-        const bool shard = repl && (plan == 1 || (plan == 0 && n >= kNjShardTips));
-        c->nj_unit_sharded = shard;
-        if (shard) { q.sh_world = c->world; q.sh_rank = c->rank; q.sh_virtual = false; q.gather = njp_gather_cb; q.gather_ctx = c; }
-        else if (ctx_vshards(c) > 1) { q.sh_world = ctx_vshards(c); q.sh_rank = 0; q.sh_virtual = true; }
-        if (c->nj_adaptive >= 0) q.adaptive = c->nj_adaptive;
-        if (int rc = njp_build(c->nj[0], c->stream)) return rc;
-        if (c->nj_adaptive >= 0) q.adaptive = c->nj_adaptive;      // (the explicit setting wins over the environment)
-    }
+    if (int rc = dist_fill(c, source, dist_type, n)) return rc;
+    if (int rc = dist_row_sums(c)) return rc;
+    if (int rc = kind == DPR_NJ_PLAN_ROWS_PRUNED ? dist_build_njr(c) : plan_is_njp(kind) ? dist_build_njp(c) : DPR_OK) return rc;
     DPR_HIP(hipEventRecord(c->ev[1], c->stream));
     DPR_HIP(hipStreamSynchronize(c->stream));
     float ms = 0;
@@ -253,19 +287,16 @@ int dpr_dist_matrix(dpr_ctx* c, int source, int dist_type, int k)
 int dpr_reserve_nj(dpr_ctx* c, int64_t n)
 {
     if (!c || n < 2 || n >= (1 << 24)) { set_error("dpr_reserve_nj: bad argument"); return DPR_ERR_ARG; }
-    const bool bionj = c->nj_variant == 1;
-    if (bionj && (c->vworld > 0 || ctx_vshards(c) > 1)) {
-        set_error("dpr_reserve_nj: BIONJ runs the single-rank streaming plan: not on a context of virtual ranks or with virtual shards (dpr_set_nj_virtual_shards > 1)");
-        return DPR_ERR_ARG;
-    }
-    if ((c->world != 1 && !bionj) || c->vworld > 0) return DPR_OK;
     DPR_HIP(hipSetDevice(c->device));
+    const int kind = ctx_nj_plan(c, n, "dpr_reserve_nj");
+    if (kind < 0) return kind;
+    // (only the plans of one rank on its own copy: the others allocate together, in dpr_dist_matrix)
+    if (kind != DPR_NJ_PLAN_SINGLE_STREAM && kind != DPR_NJ_PLAN_SINGLE_PRUNED && kind != DPR_NJ_PLAN_BIONJ) return DPR_OK;
     c->have_matrix = 0;
-    if (int rc = nj_alloc(c->nj[0], n, 0, 1, c->stream, 0, bionj)) return rc;
-    if (!bionj && want_pruned(c) && n >= 3) {
-        NjPruned& q = c->nj[0].pr;
-        if (ctx_vshards(c) > 1) { q.sh_world = ctx_vshards(c); q.sh_rank = 0; q.sh_virtual = true; }
-        if (int rc = njp_arena(q, n, c->stream)) return rc;
+    if (int rc = nj_alloc(c->nj[0], n, 0, 1, c->stream, 0, kind == DPR_NJ_PLAN_BIONJ)) return rc;
+    if (kind == DPR_NJ_PLAN_SINGLE_PRUNED) {
+        njp_set_shards(c, kind);
+        if (int rc = njp_arena(c->nj[0].pr, n, c->stream)) return rc;
     }
     DPR_HIP(hipStreamSynchronize(c->stream));
     return DPR_OK;
@@ -340,20 +371,19 @@ int64_t dpr_nj_run(dpr_ctx* c, int64_t max_iters, int32_t* merge_x, int32_t* mer
     if (c->nj_kt.stride > 0 && it0 == 0) { c->nj_kt.samples = 0; for (double& v : c->nj_kt.us_sum) v = 0; }
     c->nj_launches = 0; c->nj_collectives = 0;
     DPR_HIP(hipEventRecord(c->ev[2], c->stream));
-    if (c->nj_row_pruned) {
+    if (c->plan.kind == DPR_NJ_PLAN_ROWS_PRUNED) {
         std::vector<NjBuffers*> ranks = njr_ranks(c);
         c->nj[0].rs.launches = 0; c->nj[0].rs.collectives = 0;
         if (int rc = njr_run(ranks, it0, todo, c->stream)) return rc;
         c->nj_launches = c->nj[0].rs.launches; c->nj_collectives = c->nj[0].rs.collectives;
-    } else if (c->nj[0].pr.active) {
+    } else if (plan_is_njp(c->plan.kind)) {
         if (int rc = njp_run(c->nj[0], it0, todo, c->stream)) return rc;
     } else {
         for (int64_t k = 0; k < todo; ++k)
             if (int rc = nj_iteration(c, st.n - k, it0 + k)) return rc;
     }
     DPR_HIP(hipEventRecord(c->ev[3], c->stream));       // (the loop itself: the barrier + flush below are once per run)
-    const bool peer_plan = c->world > 1 && !c->nj_replicated && !c->nj_row_pruned && c->nj_exchange_active != kNjsLegacy;
-    if (peer_plan) {
+    if (c->plan.one_exchange_loop()) {
         // every rank must be through its pulls of the last iteration before an owner flushes the last row buffers
         if (int rc = njs_barrier(c)) return rc;
         for (auto& b : c->nj)
@@ -411,27 +441,21 @@ int64_t dpr_nj_run(dpr_ctx* c, int64_t max_iters, int32_t* merge_x, int32_t* mer
         return DPR_ERR_NOCAND;
     }
     if (last_d && st.n == 2) {
-        // D[0][1] of the final pair (src/neighborJoining.cu:245-249); row 1 lives on rank 0
+        // D[0][1] of the final pair (src/neighborJoining.cu:245-249): the row of slot 1, at the column of slot 0.  (Rows-pruned plan:
+        // every rank's finish kernel has run -- njr_run ends with a barrier over the ranks behind the finish launches; one-exchange
+        // loop: the owner's flush is behind the barrier above)
         NjBuffers& b0 = c->nj[0];
-        if (c->nj_row_pruned) {
-            // the row of slot 1 lives on its position's owner: read through the mapping of that rank's epoch buffer (every
-            // rank's finish kernel has run: njr_run ends with a barrier over the ranks behind the finish launches)
-            int32_t pos01[2];
-            DPR_HIP(hipMemcpy(pos01, b0.pr.pos_of_slot, sizeof(pos01), hipMemcpyDeviceToHost));
-            const int half = (b0.pr.epoch_index + 1) & 1, o = njr_owner(pos01[1], c->world);
-            DPR_HIP(hipMemcpy(last_d, b0.rs.peer_half[half][(size_t)o] + njr_local_row(pos01[1], c->world) * b0.pr.ld + pos01[0], sizeof(double), hipMemcpyDeviceToHost));
-        } else if (b0.pr.in_positions()) {
-            int32_t pos01[2];
-            DPR_HIP(hipMemcpy(pos01, b0.pr.pos_of_slot, sizeof(pos01), hipMemcpyDeviceToHost));
-            DPR_HIP(hipMemcpy(last_d, b0.pr.D + (int64_t)pos01[1] * b0.pr.ld + pos01[0], sizeof(double), hipMemcpyDeviceToHost));
-        } else if (c->world == 1 || c->vworld > 0 || c->nj_bionj) {
-            DPR_HIP(hipMemcpy(last_d, b0.D + 1 * b0.ld + 0, sizeof(double), hipMemcpyDeviceToHost));
-        } else if (peer_plan && !b0.peer.h_D.empty()) {
-            // rank 0's row 1 through the mapping of its matrix (its flush is behind the barrier above)
-            DPR_HIP(hipMemcpy(last_d, b0.peer.h_D[0] + 1 * b0.ld + 0, sizeof(double), hipMemcpyDeviceToHost));
+        int32_t pos01[2] = { 0, 1 };
+        if (b0.pr.in_positions()) DPR_HIP(hipMemcpy(pos01, b0.pr.pos_of_slot, sizeof(pos01), hipMemcpyDeviceToHost));
+        const double* row1 = slot_row(c, 1, pos01[1], true);
+        // real ranks on the legacy exchange hold no mapping of each other's rows: the owner sends the value in a record, and every
+        // rank, the owner included, takes part in that all-gather
+        const bool by_record = c->plan.rows_dealt() && c->vworld == 0 && c->plan.exchange == kNjsLegacy;
+        if (row1 && !by_record) {
+            DPR_HIP(hipMemcpy(last_d, row1 + pos01[0], sizeof(double), hipMemcpyDeviceToHost));
         } else {
             NjRecord rec{ 0.0, 0ull, 0.0, 0ull };
-            if (c->rank == 0) DPR_HIP(hipMemcpy(&rec.d, b0.D + 1 * b0.ld + 0, sizeof(double), hipMemcpyDeviceToHost));
+            if (row1) DPR_HIP(hipMemcpy(&rec.d, row1 + pos01[0], sizeof(double), hipMemcpyDeviceToHost));
             DPR_HIP(hipMemcpy(b0.recs + c->rank, &rec, sizeof(NjRecord), hipMemcpyHostToDevice));
             if (int rc = exchange(c, EX_RECS)) return rc;
             DPR_HIP(hipStreamSynchronize(c->stream));
@@ -464,7 +488,7 @@ int dpr_argmin_once(dpr_ctx* c, int reps, int32_t* out_i, int32_t* out_j, double
     for (auto& b : c->nj)
         if (int rc = nj_launch_select_local(b, nj_scan_grid(), c->stream)) return rc;
     if (int rc = exchange(c, EX_RECS)) return rc;
-    const int ew = c->nj_replicated ? 1 : c->world;      // ranks whose records differ
+    const int ew = c->plan.whole_matrix() ? 1 : c->world;      // ranks whose records differ
     std::vector<NjRecord> recs((size_t)ew);
     DPR_HIP(hipMemcpyAsync(recs.data(), c->nj[0].recs, sizeof(NjRecord) * (size_t)ew, hipMemcpyDeviceToHost, c->stream));
     DPR_HIP(hipStreamSynchronize(c->stream));
@@ -478,6 +502,24 @@ int dpr_argmin_once(dpr_ctx* c, int reps, int32_t* out_i, int32_t* out_j, double
     if (out_j) *out_j = (int32_t)((rec.key >> 24) & 0xFFFFFFull);
     if (out_q) *out_q = rec.q;
     return DPR_OK;
+}
+
+// the one place that chooses a plan; the table is in include/dipper_hip.h
+int dpr_nj_plan_resolve(int world, int virtual_ranks, int variant, int pruned, int multi_plan, int virtual_shards, int64_t n, uint64_t total_bytes)
+{
+    if (world < 1 || variant < 0 || variant > 1 || multi_plan < 0 || multi_plan > 3 || virtual_shards < 1 || n < 2) { set_error("dpr_nj_plan_resolve: bad argument"); return DPR_ERR_ARG; }
+    if (variant == 1) {
+        if (!virtual_ranks && virtual_shards == 1) return DPR_NJ_PLAN_BIONJ;
+        set_error("BIONJ runs the single-rank streaming plan: not on a context of virtual ranks or with virtual shards (dpr_set_nj_virtual_shards > 1)");
+        return DPR_ERR_ARG;
+    }
+    if (!pruned || n < 3) return world > 1 ? DPR_NJ_PLAN_ROWS_STREAM : DPR_NJ_PLAN_SINGLE_STREAM;
+    if (world == 1) return DPR_NJ_PLAN_SINGLE_PRUNED;
+    if (multi_plan == 3) return DPR_NJ_PLAN_ROWS_PRUNED;
+    if (virtual_ranks) return DPR_NJ_PLAN_ROWS_STREAM;       // (a context of virtual ranks keeps no whole copy per rank)
+    // auto: the two epoch buffers of a whole copy (2 x 8 n^2 bytes) no longer fit this device: deal the rows
+    if (multi_plan == 0 && 2.0 * 8.0 * (double)n * (double)n > 0.85 * (double)total_bytes) return DPR_NJ_PLAN_ROWS_PRUNED;
+    return multi_plan == 1 || (multi_plan == 0 && n >= kNjShardTips) ? DPR_NJ_PLAN_UNIT_SHARDED : DPR_NJ_PLAN_REPLICAS;
 }
 
 int dpr_njp_unit_owner(int64_t strip, int64_t group, int64_t P, int world) { return njp_unit_owner(strip, group, P, world); }
@@ -496,19 +538,20 @@ int dpr_set_nj_multi_plan(int plan)
     g_nj_multi_plan = plan;
     return DPR_OK;
 }
-int dpr_nj_is_unit_sharded(dpr_ctx* c) { return c && c->nj_unit_sharded ? 1 : 0; }
+int dpr_nj_is_unit_sharded(dpr_ctx* c) { return c && c->plan.kind == DPR_NJ_PLAN_UNIT_SHARDED ? 1 : 0; }
 // the multi-rank NJ plan the last dpr_dist_matrix set up, in words (the CLI prints it; tests assert on it)
 int dpr_get_nj_multi_info(dpr_ctx* c, char* buf, int cap)
 {
     if (!c || !buf || cap <= 0) { set_error("dpr_get_nj_multi_info: bad argument"); return DPR_ERR_ARG; }
     static const char* const ex[] = { "legacy (two all-gathers per iteration)", "peer (one all-gather, rows pulled)", "mailbox (no collective)" };
-    std::string s;
-    if (c->nj_bionj && c->world > 1) s = "BIONJ, streaming, every rank its own copy";
-    else if (c->world <= 1) s = "single rank";
-    else if (c->nj_row_pruned) s = c->nj_exchange_note;
-    else if (c->nj_replicated) s = c->nj_unit_sharded ? "pruned, matrix replicated, unit tests and scans sharded (one all-gather of block records per iteration)"
-                                                       : "pruned, every rank runs the single-GPU plan on its own copy of the matrix (replicas)";
-    else s = std::string("streaming, rows sharded block-cyclically, exchange ") + ex[c->nj_exchange_active >= 0 && c->nj_exchange_active <= 2 ? c->nj_exchange_active : 0];
+    std::string s = "single rank";
+    switch (c->plan.kind) {
+    case DPR_NJ_PLAN_BIONJ: if (c->world > 1) s = "BIONJ, streaming, every rank its own copy"; break;
+    case DPR_NJ_PLAN_ROWS_PRUNED: s = c->nj_exchange_note; break;
+    case DPR_NJ_PLAN_UNIT_SHARDED: s = "pruned, matrix replicated, unit tests and scans sharded (one all-gather of block records per iteration)"; break;
+    case DPR_NJ_PLAN_REPLICAS: s = "pruned, every rank runs the single-GPU plan on its own copy of the matrix (replicas)"; break;
+    case DPR_NJ_PLAN_ROWS_STREAM: s = std::string("streaming, rows sharded block-cyclically, exchange ") + ex[c->plan.exchange >= 0 && c->plan.exchange <= 2 ? c->plan.exchange : 0]; break;
+    }
     std::snprintf(buf, (size_t)cap, "%s", s.c_str());
     return DPR_OK;
 }
@@ -537,7 +580,7 @@ int dpr_ctx_set_nj_variant(dpr_ctx* c, int variant)
 int dpr_get_nj_lambda(dpr_ctx* c, double* out, int64_t* count)
 {
     if (!c || !count) { set_error("dpr_get_nj_lambda: null argument"); return DPR_ERR_ARG; }
-    if (!c->have_matrix || !c->nj_bionj || !c->nj[0].log_lam) { set_error("dpr_get_nj_lambda: no BIONJ matrix (dpr_ctx_set_nj_variant(ctx, 1), then dpr_dist_matrix)"); return DPR_ERR_STATE; }
+    if (!c->have_matrix || c->plan.kind != DPR_NJ_PLAN_BIONJ || !c->nj[0].log_lam) { set_error("dpr_get_nj_lambda: no BIONJ matrix (dpr_ctx_set_nj_variant(ctx, 1), then dpr_dist_matrix)"); return DPR_ERR_STATE; }
     DPR_HIP(hipSetDevice(c->device));
     NjState st;
     if (int rc = fetch_state(c, &st)) return rc;

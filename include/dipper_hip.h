@@ -241,6 +241,29 @@ int dpr_nj_is_unit_sharded(dpr_ctx *ctx);
 /* the multi-rank NJ plan the last dpr_dist_matrix set up, in words ("single rank", "pruned, every rank runs ... (replicas)",
  * "pruned, ... unit tests and scans sharded ...", "streaming, rows sharded ..., exchange ...", "row-sharded pruned NJ ...") */
 int dpr_get_nj_multi_info(dpr_ctx *ctx, char *buf, int cap);
+/* The NJ plan of a context: one of these kinds, chosen by dpr_nj_plan_resolve and by nothing else. */
+#define DPR_NJ_PLAN_SINGLE_STREAM 0 /* one rank, full Q scan every iteration */
+#define DPR_NJ_PLAN_SINGLE_PRUNED 1 /* one rank, exact pruned scan (with dpr_set_nj_virtual_shards: emulated unit shards) */
+#define DPR_NJ_PLAN_BIONJ 2         /* BIONJ: the streaming loop on this rank's own whole copy, whatever the world */
+#define DPR_NJ_PLAN_ROWS_STREAM 3   /* several ranks, rows dealt block-cyclically, streaming (dpr_ctx_set_nj_exchange) */
+#define DPR_NJ_PLAN_REPLICAS 4      /* several ranks, each runs the single-GPU pruned plan on its own whole copy */
+#define DPR_NJ_PLAN_UNIT_SHARDED 5  /* several ranks, whole copy each, unit tests and scans of an iteration shared */
+#define DPR_NJ_PLAN_ROWS_PRUNED 6   /* several ranks, rows dealt, exact pruned scan (njr.hip) */
+/* Host-only, pure (no device, no environment): the kind that dpr_dist_matrix sets up for n tips, or DPR_ERR_ARG.  world: ranks
+ * of the context; virtual_ranks: they all live in one context (dpr_create_virtual); variant: dpr_ctx_set_nj_variant; pruned:
+ * the NJ mode asks for the pruned scan; multi_plan 0..3: dpr_set_nj_multi_plan; virtual_shards >= 1; total_bytes: the device's
+ * memory, read by the auto rule of real ranks only.  In this order:
+ *   BIONJ                               virtual ranks or virtual shards > 1: DPR_ERR_ARG; else BIONJ, for any world (several real
+ *                                       ranks: each keeps its own copy, allocated as rank 0 of 1)
+ *   streaming wanted, or n < 3          world 1: SINGLE_STREAM; else ROWS_STREAM, whatever multi_plan says
+ *   world 1                             SINGLE_PRUNED (virtual shards are a detail of that plan)
+ *   multi_plan 3                        ROWS_PRUNED, virtual or real ranks
+ *   virtual ranks, multi_plan 0, 1, 2   ROWS_STREAM, whatever the memory says (a context of virtual ranks keeps no whole copies)
+ *   real ranks, multi_plan 1 / 2        UNIT_SHARDED / REPLICAS
+ *   real ranks, multi_plan 0            16.0 * n * n > 0.85 * total_bytes (two epoch buffers of a whole copy do not fit):
+ *                                       ROWS_PRUNED; else UNIT_SHARDED from 65 536 tips on, REPLICAS below */
+int dpr_nj_plan_resolve(int world, int virtual_ranks, int variant, int pruned, int multi_plan, int virtual_shards, int64_t n,
+                        uint64_t total_bytes);
 /* The three plan knobs above are process-wide DEFAULTS.  Per context (two contexts of one process may run different
  * plans): same meaning, value -1 = follow the process-wide default again; effective at that context's next
  * dpr_dist_matrix. */
