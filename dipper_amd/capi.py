@@ -143,6 +143,7 @@ def load_library():
     L.dpr_ctx_set_place_fixed_batch.argtypes = [C.c_void_p, C.c_int64]
     L.dpr_get_place_fixed_timing.argtypes = [C.c_void_p, c_f64p, c_f64p]
     L.dpr_njp_unit_owner.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    L.dpr_place_policy_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_f64p, c_f64p, C.c_int64, c_i32p]
     L.dpr_nj_plan_resolve.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint64]
     L.dpr_dc_query_share.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dpr_dc_deal_clusters.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int, c_i32p]
@@ -246,6 +247,19 @@ def nj_plan_resolve(world, virtual_ranks, variant, pruned, multi_plan, virtual_s
     raises DipperError where dist_matrix would refuse"""
     L = load_library()
     return _chk(L, L.dpr_nj_plan_resolve(world, int(virtual_ranks), variant, int(pruned), multi_plan, virtual_shards, n, total_bytes))
+
+
+def place_policy_run(source, world, window_transport, no_overlap, multi_min, first, last, batch_rows, tree_ms, dist_alone_ms):
+    """the overlap policy of place_run over a described run (host only): per batch of batch_rows tips from `first` on, whether its
+    distance rows are produced beside the previous batch's tree kernels; tree_ms / dist_alone_ms: one figure per batch"""
+    L = load_library()
+    tree = np.ascontiguousarray(tree_ms, dtype=np.float64)
+    dist = np.ascontiguousarray(dist_alone_ms, dtype=np.float64)
+    assert tree.shape == dist.shape and tree.ndim == 1
+    beside = np.zeros(max(len(tree), 1), dtype=np.int32)
+    _chk(L, L.dpr_place_policy_run(source, world, int(window_transport), int(no_overlap), multi_min, first, last, batch_rows,
+                                   _p(tree, c_f64p), _p(dist, c_f64p), len(tree), _p(beside, c_i32p)))
+    return [bool(b) for b in beside[:len(tree)]]
 
 
 def _p(a, t):

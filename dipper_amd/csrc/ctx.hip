@@ -172,9 +172,6 @@ int dpr_destroy(dpr_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     shm_comm_free(c);
-    for (hipEvent_t e : c->place_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->place_ev_busy) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->place_ev_tree) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->nj_kt.ev) (void)hipEventDestroy(e);
     lap("events destroyed");
     for (auto& b : c->nj) nj_free(b);

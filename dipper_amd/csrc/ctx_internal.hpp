@@ -1,5 +1,5 @@
 // Shared by the translation units that implement the C ABI (ctx.hip: context, inputs, hooks; ctx_comm.hip: RCCL, peer
-// windows, exchanges; ctx_nj.hip: distance matrix + NJ plans; ctx_place.hip: placement, exact mode, divide-and-conquer, fixed-backbone placement).
+// windows, exchanges; ctx_nj.hip: distance matrix + NJ plans; ctx_place.hip: placement, exact mode, divide-and-conquer, fixed-backbone placement, with place_rows.hpp).
 #pragma once
 #include "dpr_internal.hpp"
 
@@ -69,11 +69,8 @@ struct dpr_ctx {
     dpr::NjPlan plan;                // what the last dpr_dist_matrix set up
     double dist_ms = 0, nj_ms = 0;
     double place_dist_ms = 0;        // distance rows of the last placement run (the rest of nj_ms is tree work)
-    std::vector<hipEvent_t> place_ev;   // event pairs whose sum is the reported distance part of the current placement run
-    std::vector<hipEvent_t> place_ev_busy;   // overlap mode: event pairs around the distance batches on the second stream
     double place_dist_busy_ms = 0;      // overlap mode: time the distance batches were in flight beside the tree kernels
     bool place_overlapped = false;      // some batch of the last placement run was produced beside the tree kernels
-    std::vector<hipEvent_t> place_ev_tree;   // per-batch event pairs around the tree kernels (the overlap policy's probes)
     int64_t place_batches = 0, place_batches_overlapped = 0;      // of the last placement run
     dpr::DcStats dc_stats;
     double dc_ms[3] = { 0, 0, 0 };   // backbone, cluster assignment, cluster trees

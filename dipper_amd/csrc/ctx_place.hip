@@ -1,7 +1,10 @@
-// C ABI, tree builders that place tips: k-closest placement (batches of distance rows, overlap policy), exact placement mode,
-// divide-and-conquer, fixed-backbone placement; dpr_place_run, dpr_place_exact_run, dpr_dc_run, dpr_place_fixed_set / _run and their
-// getters.
-#include "ctx_internal.hpp"
+// C ABI, tree builders that place tips: k-closest placement (batches of distance rows: place_rows.hpp; which of them run beside the
+// tree kernels: place_policy.hpp), exact placement mode, divide-and-conquer, fixed-backbone placement; dpr_place_run,
+// dpr_place_policy_run, dpr_place_exact_run, dpr_dc_run, dpr_place_fixed_set / _run and their getters.
+#include "place_policy.hpp"
+#include "place_rows.hpp"
+
+#include <array>
 
 using namespace dpr;
 
@@ -19,6 +22,17 @@ static int check_source(dpr_ctx* c, const char* fn, int source, int k, int64_t n
         if (!c->packed_lower || c->n_input != n) { set_error(f + ": call dpr_set_matrix_lower first"); return DPR_ERR_STATE; }
     } else { set_error(f + ": unknown source"); return DPR_ERR_ARG; }
     return DPR_OK;
+}
+
+// queries per batch of a block of distances from nq queries to all m backbone tips: the block stays below 2 GiB, between 256 and
+// 8192 queries, a multiple of 256, no more than the queries there are (dpr_dc_run's assignment, dpr_place_fixed_run)
+static int64_t query_batch(int64_t m, int64_t nq)
+{
+    int64_t Q = ((int64_t)1 << 31) / (8 * m) / 256 * 256;
+    if (Q < 256) Q = 256;
+    if (Q > 8192) Q = 8192;
+    if (Q > (nq + 255) / 256 * 256) Q = (nq + 255) / 256 * 256;
+    return Q;
 }
 
 // c->place for n tips again; the fixed backbone of dpr_place_fixed_set lived in the old arrays
@@ -68,244 +82,78 @@ static int copy_adjacency(dpr_ctx* c, int64_t n, bool to_device, int32_t* head, 
     return DPR_OK;
 }
 
-// distance rows of a source: MSA and Mash rows are computed into a buffer, the packed triangle is read in place
-struct RowSource {
-    dpr_ctx* c;
-    int source, dist_type;
-    // rows [i0, i0 + nr) x columns [0, ncols) into out (row stride ld; transposed: column stride ld)
-    int fill(int64_t i0, int64_t nr, double* out, int64_t ld, int64_t ncols, hipStream_t st, bool transposed = false) const
-    {
-        if (nr <= 0) return DPR_OK;
-        if (source == DPR_SRC_MSA) return msa_dist_block_rows(c->msa, i0, nr, 0, 0, ncols, dist_type, out, ld, st, transposed);
-        if (source == DPR_SRC_MASH) return mash_dist_rows(c->mash, i0, nr, 0, 0, false, ncols, out, ld, st, transposed);
-        return DPR_OK;
-    }
-    // row i of a buffer that starts at row i0 (row stride ld), or of the packed triangle
-    const double* row_ptr(int64_t i, int64_t i0, const double* rows, int64_t ld) const
-    {
-        return source == DPR_SRC_MATRIX ? c->packed_lower + i * (i - 1) / 2 : rows + (i - i0) * ld;
-    }
-};
-
 extern "C" {
+
+// what is fixed for a placement run's overlap policy; the environment is read here, once
+static PlacePolicy::Fixed place_policy_fixed(const dpr_ctx* c, int source)
+{
+    const bool ranks = comm_real(c) && source != DPR_SRC_MATRIX;      // several real ranks share every batch
+    const char* e = std::getenv("DPR_PLACE_BATCH");
+    return PlacePolicy::fixed_for(source == DPR_SRC_MASH, ranks, !c->comm, std::getenv("DPR_PLACE_NO_OVERLAP") != nullptr, place_multi_min(), e ? std::atoll(e) : 0);
+}
 
 // k-closest placement of tips [first, last) into c->place (findPlacementTree / addQuery loop,
 // src/placement_close_k.cu:756-851,888-987; findBackboneTreeDC, src/divide_and_conquer/
-// placement_close_k.cu:832-925): distance rows in batches of 256 (1024 for Mash input) from the row providers.
+// placement_close_k.cu:832-925): distance rows in batches from the row pipeline, each batch produced on the main stream or beside
+// the previous batch's tree kernels as the overlap policy says (place_policy.hpp).
 // first == 2 starts from the two-tip tree, otherwise the imported backbone is already in the arrays.
-static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int64_t last)
+static int place_range_batches(dpr_ctx* c, RowPipeline& pipe, PlacePolicy& pol, int64_t first, int64_t last)
 {
     PlaceBuffers& p = c->place;
-    // distance rows per batch: 1024 for Mash input, whose batches run beside the tree kernels (100 000 unaligned tips:
-    // 3.81 / 3.60 / 3.93 s with 256 / 1024 / 4096 -- fewer launch tails, but a longer start-up without overlap)
-    int64_t R = source == DPR_SRC_MASH ? 1024 : 256;
-    if (const char* e = std::getenv("DPR_PLACE_BATCH")) { const int64_t v = std::atoll(e); if (v >= 16 && v <= 65536) R = v; }
-    const int64_t ldb = (last + 15) / 16 * 16;
-    // Multi-GPU (dpr_comm_init done, inputs replicated): the distance rows of a batch do not depend on the
-    // placements, so every rank computes R/world of them and one all-gather per batch completes the block;
-    // the tree kernels then run identically on every rank (deterministic), so no tree state is exchanged.
-    const bool sharded = comm_real(c) && source != DPR_SRC_MATRIX;
-    const int W = sharded ? c->world : 1;
-    const int64_t per = (R + W - 1) / W;         // rows per rank and batch
-    // The distance rows of the NEXT batch may be produced on a second stream while the tree kernels of the current batch run
-    // (they are latency-bound and occupy a few workgroups; the pair kernels fill the rest of the chip): two row buffers, the
-    // producer waits for the batch that last read the buffer it overwrites.  Mash input only: with aligned input the distance part
-    // is 4 % of the run and the contention costs more than it hides (1.63 -> 1.82 s at 100 000 tips).
-    // Round 4: the decision is taken PER BATCH.  Overlap pays while a batch's distance part is the SHORTER one -- it then
-    // disappears behind the tree kernels (100 000 unaligned tips from scratch: 3.2 -> 2.5 s).  Where it is the longer one
-    // nothing can hide it, and sharing the chip slows both sides: adding 50 000 queries to a 500 000-tip backbone, every batch is
-    // 5 x 10^8 pairs (~100 ms alone) against ~50 ms of tree kernels; overlapped, the pair kernel ran at half its rate and the
-    // update kernel 5.6 x slower (profiles/r3/kernel_stats_add_mash_500k_plus_50k.csv): 9.2 s where back to back is 7.6 s.
-    // So: batch k + 1 is produced beside batch k's tree kernels iff its predicted time alone (pairs / the rate measured on this
-    // run's batches that ran alone, 4.5 G pairs/s until there is one) is below the tree time of the latest finished batch
-    // (deflated by 1.4 if that batch shared the chip); otherwise it is produced on the main stream right before its own tips, at
-    // full chip.  Measured (profiles/r4/place_policy_*.jsonl): --add 500 000 + 50 000 through Mash 8.87 s (every batch beside)
-    // -> 6.56 s (none); 100 000 tips from scratch 3.07 s (none) / 2.52 s (every batch) / 2.5x s (policy).  The host waits for batch k - 1 before it decides about batch k + 1 (it never runs more than one batch ahead
-    // of the device any more; enqueueing is ~10 x faster than the tree kernels execute, so the device does not starve).
-    // Round 5: while the tree kernels are the one-tip launch pairs (a 780-block scan and a one-workgroup update every 15 us) EVERY
-    // batch goes beside them, longer than the tree part or not -- 100 000 unaligned tips 2.18 -> 1.72 s (mean branch 2e-5), 2.30 ->
-    // 2.14 s (1e-3).  The rule above stays for the four-tip launch pairs (>= 150 000 tips): their scan fills the chip for 54 us of
-    // every ~120, so the pair kernel beside it gets half a chip (--add through Mash, every batch beside: 6.8 s against 4.0 s; the
-    // 1 024-thread update workgroup needs an empty CU and waits 0.5 ms for one).
-    // Results cannot depend on the policy: the rows are the same numbers whichever stream produced them.
-    // (ranks on the window transport of dpr_comm_init_shared: its all-gather is synchronous with the host, nothing would overlap)
-    const bool overlap_allowed = source == DPR_SRC_MASH && !std::getenv("DPR_PLACE_NO_OVERLAP") && !(sharded && !c->comm);
-    // (several ranks: every rank must take the same decisions -- the batches' all-gathers are enqueued on the stream the decision
-    //  picks -- and a rank's share of a batch is 1 / G of the pairs, i.e. the short side: every batch beside, as in round 3)
-    const bool overlap_always = overlap_allowed && sharded;
-    DevBuf<double> rows_buf[2];
-    if (source != DPR_SRC_MATRIX) {
-        DPR_HIP(rows_buf[0].alloc((size_t)(per * W * ldb)));
-        if (overlap_allowed) {
-            const hipError_t me = rows_buf[1].alloc((size_t)(per * W * ldb));
-            if (me != hipSuccess) return hip_fail(me, "hipMalloc(second row buffer)");
-        }
+    const int64_t R = pol.fixed().R;
+    if (first == 2) {
+        if (int rc = place_init_fresh(p, c->stream)) return rc;
+        if (int rc = pipe.src.fill(1, 1, pipe.rows(0), pipe.ldb, 2, c->stream)) return rc;
+        if (int rc = place_initial_tree(p, pipe.src.row_ptr(1, 1, pipe.rows(0), pipe.ldb), c->stream)) return rc;
+    } else {
+        if (int rc = place_import_backbone(p, first, c->stream)) return rc;
     }
-    if (overlap_allowed && !c->stream2) {
-        // lowest priority: the distance kernels fill the chip, the tree kernels of the current batch (one wavefront or a few
-        // blocks each, on the context's stream) must not queue behind them
-        int least = 0, greatest = 0;
-        DPR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        DPR_HIP(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, least));
-    }
-    std::vector<ScopedEvent> sync_ev;                            // fill-done / tree-done events of this run
-    auto new_event = [&](hipEvent_t* e) -> int { sync_ev.emplace_back(); DPR_HIP(hipEventCreateWithFlags(sync_ev.back().put(), hipEventDisableTiming)); *e = sync_ev.back(); return DPR_OK; };
-    const RowSource src{ c, source, dist_type };
-    auto fill_some = [&](int64_t i0, int64_t nr, double* out, hipStream_t st) -> int { return src.fill(i0, nr, out, ldb, i0 + nr, st); };
-    auto fill_rows_inner = [&](int64_t i0, int64_t nr, double* rows, hipStream_t ds) -> int {
-        if (!sharded) return fill_some(i0, nr, rows, ds);
-        const int64_t a = (int64_t)c->rank * per, b = a + per < nr ? a + per : nr;     // this rank's rows of the batch
-        if (int rc = fill_some(i0 + a, b - a, rows + a * ldb, ds)) return rc;
-        return comm_all_gather(c, rows + a * ldb, rows, sizeof(double) * (size_t)(per * ldb), ds);
-    };
-    // the reference reports the distance and the tree part of a placement run separately
-    // (src/placement_close_k.cu:852-853,985-986).  A batch produced on the main stream: an event pair around it (c->place_ev).
-    // A batch produced beside the tree kernels: its own interval overlaps the tree work in wall time (and stretches while it
-    // shares the chip) -- kept as `busy` time (c->place_ev_busy); what counts as distance time is the time the tree stream
-    // actually WAITED for it (an event pair around the wait, c->place_ev), so distance + tree = the run's wall time again.
-    c->place_overlapped = false;
-    c->place_batches = 0; c->place_batches_overlapped = 0;
-    auto fill_rows = [&](int64_t i0, int64_t nr, double* rows, bool beside, hipEvent_t* t0, hipEvent_t* t1) -> int {
-        hipStream_t ds = beside ? c->stream2 : c->stream;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (source != DPR_SRC_MATRIX) {
-            std::vector<hipEvent_t>& dst = beside ? c->place_ev_busy : c->place_ev;      // (handed over one by one: nothing is lost if the second create fails)
-            DPR_HIP(hipEventCreate(&e0)); dst.push_back(e0);
-            DPR_HIP(hipEventCreate(&e1)); dst.push_back(e1);
-            DPR_HIP(hipEventRecord(e0, ds));
-        }
-        c->mash.share_chip = beside;
-        const int rc = fill_rows_inner(i0, nr, rows, ds);
-        c->mash.share_chip = false;
-        if (e1) DPR_HIP(hipEventRecord(e1, ds));
-        if (t0) *t0 = e0;
-        if (t1) *t1 = e1;
-        return rc;
-    };
-    auto run = [&]() -> int {
-        if (first == 2) {
-            if (int rc = place_init_fresh(p, c->stream)) return rc;
-            if (int rc = fill_some(1, 1, rows_buf[0], c->stream)) return rc;
-            if (int rc = place_initial_tree(p, src.row_ptr(1, 1, rows_buf[0], ldb), c->stream)) return rc;
-        } else {
-            if (int rc = place_import_backbone(p, first, c->stream)) return rc;
-        }
-        if (first >= last) return DPR_OK;
-        hipEvent_t filled[2] = { nullptr, nullptr }, consumed[2] = { nullptr, nullptr };
-        bool ahead = false;                       // the rows of the batch about to be placed were produced beside the previous batch
-        // policy state: what a batch that ran alone cost
-        double tree_ms_per_tip = -1.0, pairs_per_ms = 4.5e6;
-        struct Probe { hipEvent_t d0, d1, t0, t1; double pairs; int64_t nr; bool dist_alone, tree_alone; };
-        std::vector<Probe> probes;                // one per batch
-        size_t harvested = 0;
-        auto batch_pairs = [&](int64_t i0, int64_t nr) { return (double)nr * ((double)i0 + 0.5 * (double)(nr - 1)); };
-        auto harvest = [&](size_t upto) -> int {  // read the timings of the batches < upto (host waits for the last of them)
-            for (; harvested < upto; ++harvested) {
-                Probe& pr = probes[harvested];
-                if (!pr.t1) continue;
-                DPR_HIP(hipEventSynchronize(pr.t1));
-                float ms = 0;
-                // (tree kernels that shared the chip with a distance batch ran ~1.3 x slower at 100 000 tips: such a batch's time
-                //  is deflated by 1.4 before it stands for "the tree part alone" -- the tree part grows with the tree, so the
-                //  latest batch is the better estimate than batch 0's clean one)
-                if (hipEventElapsedTime(&ms, pr.t0, pr.t1) == hipSuccess && pr.nr > 0) tree_ms_per_tip = (double)ms / (double)pr.nr / (pr.tree_alone ? 1.0 : 1.4);
-                if (pr.dist_alone && pr.d0 && pr.d1 && pr.pairs >= 5.0e7 && hipEventElapsedTime(&ms, pr.d0, pr.d1) == hipSuccess && ms > 0.0f)
-                    pairs_per_ms = pr.pairs / (double)ms;
+    size_t k = 0;
+    for (int64_t i0 = first; i0 < last; i0 += R, ++k) {
+        const int64_t nr = last - i0 < R ? last - i0 : R;
+        if (int rc = pipe.make_available(k, i0, nr, pol.ahead())) return rc;
+        ++c->place_batches;
+        // the next batch beside this batch's tree kernels?  (the timed rule alone makes the host wait, for batch k - 1)
+        if (pol.needs_timings(i0, nr))
+            while (pol.observed() < k) {
+                double tree_ms = 0, dist_ms = 0;
+                if (int rc = pipe.t.wait_batch(pol.observed(), &tree_ms, &dist_ms)) return rc;
+                pol.observe(tree_ms, dist_ms);
             }
-            return DPR_OK;
-        };
-        int64_t i0 = first;
-        int cur = 0;
-        for (size_t k = 0; i0 < last; i0 += R, cur ^= 1, ++k) {
-            const int64_t nr = last - i0 < R ? last - i0 : R;
+        if (pol.decide(i0, nr)) {
             const int64_t j0 = i0 + R;
-            double* rows = rows_buf[overlap_allowed ? cur : 0];
-            Probe pr{ nullptr, nullptr, nullptr, nullptr, batch_pairs(i0, nr), nr, false, true };
-            if (!ahead) {
-                // this batch's rows on the main stream, at full chip (a buffer's last reader ran on this stream: ordered)
-                if (int rc = fill_rows(i0, nr, rows, false, &pr.d0, &pr.d1)) return rc;
-                pr.dist_alone = true;
-            } else {
-                hipEvent_t w0 = nullptr, w1 = nullptr;
-                DPR_HIP(hipEventCreate(&w0)); c->place_ev.push_back(w0);
-                DPR_HIP(hipEventCreate(&w1)); c->place_ev.push_back(w1);
-                DPR_HIP(hipEventRecord(w0, c->stream));
-                DPR_HIP(hipStreamWaitEvent(c->stream, filled[cur], 0));
-                DPR_HIP(hipEventRecord(w1, c->stream));
-            }
-            ++c->place_batches;
-            // the next batch beside this batch's tree kernels?
-            bool next_ahead = false;
-            if (overlap_allowed && j0 < last) {
-                const int64_t nr2 = last - j0 < R ? last - j0 : R;
-                if (overlap_always || i0 + nr <= place_multi_min()) next_ahead = true;      // (one tip per launch pair: always, see above)
-                else {
-                    if (k >= 1) { if (int rc = harvest(k)) return rc; }      // batches 0 .. k-1 (the host waits for batch k-1 here)
-                    const double dist_alone_ms = batch_pairs(j0, nr2) / pairs_per_ms;
-                    // (no tree timing yet -- this is batch 0: its successor is produced alone too, unless its distance part is tiny)
-                    next_ahead = tree_ms_per_tip > 0.0 ? dist_alone_ms < tree_ms_per_tip * (double)nr : dist_alone_ms < 1.0;
-                }
-                if (next_ahead) {
-                    const int nb = cur ^ 1;
-                    if (consumed[nb]) DPR_HIP(hipStreamWaitEvent(c->stream2, consumed[nb], 0));
-                    else {
-                        // (first use of that buffer by the second stream: everything enqueued so far may still read it)
-                        hipEvent_t e;
-                        if (int rc = new_event(&e)) return rc;
-                        DPR_HIP(hipEventRecord(e, c->stream));
-                        DPR_HIP(hipStreamWaitEvent(c->stream2, e, 0));
-                    }
-                    if (int rc = fill_rows(j0, nr2, rows_buf[nb], true, nullptr, nullptr)) return rc;
-                    if (int rc = new_event(&filled[nb])) return rc;
-                    DPR_HIP(hipEventRecord(filled[nb], c->stream2));
-                    c->place_overlapped = true;
-                    ++c->place_batches_overlapped;
-                    pr.tree_alone = false;
-                }
-            }
-            if (source != DPR_SRC_MATRIX) {
-                DPR_HIP(hipEventCreate(&pr.t0)); c->place_ev_tree.push_back(pr.t0);
-                DPR_HIP(hipEventCreate(&pr.t1)); c->place_ev_tree.push_back(pr.t1);
-                DPR_HIP(hipEventRecord(pr.t0, c->stream));
-            }
-            if (source == DPR_SRC_MATRIX) {      // packed triangle: rows are not evenly spaced
-                for (int64_t i = i0; i < i0 + nr; ++i)
-                    if (int rc = place_tip(p, src.row_ptr(i, i0, rows, ldb), i, c->place_trace, c->stream)) return rc;
-            } else {
-                if (int rc = place_tips(p, rows, ldb, i0, nr, c->place_trace, c->stream)) return rc;
-            }
-            if (pr.t1) DPR_HIP(hipEventRecord(pr.t1, c->stream));
-            if (overlap_allowed) { if (int rc = new_event(&consumed[cur])) return rc; DPR_HIP(hipEventRecord(consumed[cur], c->stream)); }
-            probes.push_back(pr);
-            ahead = next_ahead;
+            if (int rc = pipe.produce_beside(k + 1, j0, last - j0 < R ? last - j0 : R)) return rc;
+            c->place_overlapped = true;
+            ++c->place_batches_overlapped;
         }
-        return DPR_OK;
-    };
-    const int rc = run();
-    c->mash.share_chip = false;
-    if (rows_buf[0] || rows_buf[1]) {     // both streams are done with the row buffers before the scope releases them
-        (void)hipStreamSynchronize(c->stream);
-        if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+        const double* rows = pipe.rows(k);
+        if (pipe.timed()) { if (int rc = pipe.t.tree.begin(c->stream)) return rc; }
+        if (pipe.src.source == DPR_SRC_MATRIX) {      // packed triangle: rows are not evenly spaced
+            for (int64_t i = i0; i < i0 + nr; ++i)
+                if (int rc = place_tip(p, pipe.src.row_ptr(i, i0, rows, pipe.ldb), i, c->place_trace, c->stream)) return rc;
+        } else {
+            if (int rc = place_tips(p, rows, pipe.ldb, i0, nr, c->place_trace, c->stream)) return rc;
+        }
+        if (pipe.timed()) { if (int rc = pipe.t.tree.end(c->stream)) return rc; }
+        if (int rc = pipe.mark_consumed(k)) return rc;
     }
-    return rc;
+    return DPR_OK;
 }
 
-// sum of the distance-batch event pairs of the run that just finished (stream idle); the events are released
-static void place_collect_dist_ms(dpr_ctx* c)
+// the scope of one run: policy and row pipeline (with the run's timers) live here; both streams are drained and the run's figures read on success
+// and on failure, and every event of the run is released with the scope
+static int place_range(dpr_ctx* c, int source, int dist_type, int64_t first, int64_t last)
 {
-    auto sum = [](std::vector<hipEvent_t>& evs) {
-        double tot = 0;
-        for (size_t i = 0; i + 1 < evs.size(); i += 2) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, evs[i], evs[i + 1]) == hipSuccess) tot += ms;
-        }
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-        evs.clear();
-        return tot;
-    };
-    c->place_dist_ms = sum(c->place_ev);
-    c->place_dist_busy_ms = sum(c->place_ev_busy);
-    (void)sum(c->place_ev_tree);       // (the policy's probes; released here)
+    c->place_overlapped = false;
+    c->place_batches = 0; c->place_batches_overlapped = 0;
+    c->place_dist_ms = 0; c->place_dist_busy_ms = 0;
+    PlacePolicy pol(place_policy_fixed(c, source), last);
+    RowPipeline pipe(c, source, dist_type);
+    if (int rc = pipe.init(pol.fixed().R, last, pol.fixed().allowed)) return rc;
+    const int rc = place_range_batches(c, pipe, pol, first, last);
+    pipe.drain();
+    pipe.t.finish(c);
+    return rc;
 }
 
 // dist_ms: the part of the run the tree kernels could not proceed for want of distance rows (without overlap: the
@@ -338,6 +186,28 @@ int dpr_get_place_policy(dpr_ctx* c, int64_t* batches, int64_t* overlapped_batch
     return DPR_OK;
 }
 
+// the policy over a described run: the loop of place_range_batches without the device
+int dpr_place_policy_run(int source, int world, int window_transport, int no_overlap, int64_t multi_min, int64_t first, int64_t last,
+                         int64_t batch_rows, const double* tree_ms, const double* dist_alone_ms, int64_t batches, int32_t* beside)
+{
+    if (source < DPR_SRC_MSA || source > DPR_SRC_MATRIX || world < 1 || first < 2 || last < first || batches < 0 || (batches > 0 && (!tree_ms || !dist_alone_ms || !beside))) {
+        set_error("dpr_place_policy_run: bad argument");
+        return DPR_ERR_ARG;
+    }
+    PlacePolicy pol(PlacePolicy::fixed_for(source == DPR_SRC_MASH, world > 1 && source != DPR_SRC_MATRIX, window_transport != 0, no_overlap != 0, multi_min, batch_rows), last);
+    const int64_t R = pol.fixed().R;
+    if (batches != (last - first + R - 1) / R) { set_error("dpr_place_policy_run: tips [first, last) in batches of " + std::to_string(R) + " rows are " + std::to_string((last - first + R - 1) / R) + " batches"); return DPR_ERR_ARG; }
+    size_t k = 0;
+    for (int64_t i0 = first; i0 < last; i0 += R, ++k) {
+        const int64_t nr = last - i0 < R ? last - i0 : R;
+        if (pol.needs_timings(i0, nr))
+            for (size_t b = pol.observed(); b < k; ++b) pol.observe(tree_ms[b], dist_alone_ms[b]);
+        beside[k] = pol.ahead() ? 1 : 0;
+        pol.decide(i0, nr);
+    }
+    return DPR_OK;
+}
+
 int dpr_place_run(dpr_ctx* c, int source, int dist_type, int k, int64_t first, int64_t n, int32_t* head,
                   int32_t* e, int32_t* nxt, int32_t* belong, double* len)
 {
@@ -351,14 +221,13 @@ int dpr_place_run(dpr_ctx* c, int source, int dist_type, int k, int64_t first, i
     DPR_HIP(hipMemsetAsync(p.misc + 2, 0, 2 * sizeof(int32_t), c->stream));      // fallback counters of the four-tip launches (dpr_get_place_walks)
     if (first > 2) { if (int rc = copy_adjacency(c, n, true, head, e, nxt, belong, len)) return rc; }
     DPR_HIP(hipEventRecord(c->ev[2], c->stream));
-    if (int rc = place_range(c, source, dist_type, first, n)) { place_collect_dist_ms(c); return rc; }
+    if (int rc = place_range(c, source, dist_type, first, n)) return rc;
     DPR_HIP(hipEventRecord(c->ev[3], c->stream));
     if (int rc = copy_adjacency(c, n, false, head, e, nxt, belong, len)) return rc;
     DPR_HIP(hipStreamSynchronize(c->stream));
     float ms = 0;
     DPR_HIP(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
     c->nj_ms = ms;
-    place_collect_dist_ms(c);
     if (log_level("place") > 0) {
         int64_t st[6] = { 0, 0, 0, 0, 0, 0 };
         if (dpr_get_place_walks(c, nullptr, st) == DPR_OK)
@@ -445,6 +314,133 @@ int dpr_get_exact_state(dpr_ctx* c, int32_t* rev, int32_t* dep)
 }
 
 // ---- divide-and-conquer mode ------------------------------------------------------------------------
+// one dpr_dc_run: what its three steps share.  Everything is released when the run ends (the stream is idle by then on success;
+// hipFree waits otherwise), nothing earlier: the budget of the cluster trees is read from the free memory as it stands then.
+struct DcRun {
+    dpr_ctx* c;
+    int source, dist_type, flags;
+    int64_t n, B;
+    bool real;                       // ranks: RCCL ranks of dpr_comm_init, or -- validation on one GPU -- DPR_DC_VIRTUAL_RANKS(w) emulated in turn
+    int W;
+    ScopedEvent ev[4];               // backbone | assignment | cluster trees |
+    DevBuf<int32_t> d_cl;
+    DevBuf<uint64_t> snap_old, snap_acc;
+    DcTable tab;
+    std::vector<int32_t> h_cl;       // cluster of every tip, -1 for the backbone
+    ~DcRun() { dc_table_free(tab); }
+};
+
+// the arrays a cluster tree changes, as 64-bit words, each with its offset in a snapshot of all of them
+struct DcArr { void* cur; int64_t words, off; };
+static std::array<DcArr, 9> dc_arrays(const DcRun& r)
+{
+    const PlaceBuffers& p = r.c->place;
+    const int64_t n = r.n;
+    std::array<DcArr, 9> arrs{ { { p.head, n, 0 }, { p.e, 4 * n, 0 }, { p.nxt, 4 * n, 0 }, { p.belong, 4 * n, 0 }, { p.rev, 4 * n, 0 },
+                                 { p.len, 8 * n, 0 }, { p.cid, 20 * n, 0 }, { p.cdis, 40 * n, 0 }, { r.c->place_trace, 3 * n, 0 } } };
+    for (size_t i = 1; i < arrs.size(); ++i) arrs[i].off = arrs[i - 1].off + arrs[i - 1].words;
+    return arrs;
+}
+
+// backbone tree: tips [0, B) (findBackboneTreeDC)
+static int dc_backbone(DcRun& r)
+{
+    dpr_ctx* c = r.c;
+    DPR_HIP(hipEventRecord(r.ev[0], c->stream));
+    if (int rc = place_range(c, r.source, r.dist_type, 2, r.B)) return rc;
+    DPR_HIP(hipEventRecord(r.ev[1], c->stream));
+    return DPR_OK;
+}
+
+// cluster assignment of tips [B, n) (findClustersDC).  Multi-GPU: the backbone is built identically on every rank (same inputs,
+// deterministic kernels); the queries are independent, so each rank assigns a contiguous share and the ids are summed (zeros
+// elsewhere) over RCCL.
+static int dc_assign_queries(DcRun& r)
+{
+    dpr_ctx* c = r.c;
+    const int64_t n = r.n, B = r.B;
+    const RowSource src{ c, r.source, r.dist_type };
+    if (int rc = dc_table_build(c->place, B, r.tab, c->stream)) return rc;
+    const int64_t Q = query_batch(B, n - B);
+    DevBuf<double> dT;      // (released before the budget of the cluster trees is read)
+    DPR_HIP(dT.alloc((size_t)(B * Q)));
+    DPR_HIP(r.d_cl.alloc((size_t)(n + 1)));
+    DPR_HIP(hipMemsetAsync(r.d_cl, 0, sizeof(int32_t) * (size_t)(n + 1), c->stream));
+    // the reference's aligned-input kernel never writes the distance to backbone tip B-1
+    // (src/divide_and_conquer/msa.cu:331 `idx>=ed-st`) and scans the 0.0 of a fresh allocation
+    const bool skip_last = r.source == DPR_SRC_MSA && !(r.flags & DPR_DC_EXACT_LAST);
+    auto assign = [&]() -> int {
+        for (int v = 0; v < r.W; ++v) {
+            if (r.real && v != c->rank) continue;     // virtual ranks: every share is processed here, one after the other
+            int64_t q0 = 0, q1 = 0;
+            dc_query_share(n, B, v, r.W, &q0, &q1);
+            for (int64_t i0 = q0; i0 < q1; i0 += Q) {
+                const int64_t nr = q1 - i0 < Q ? q1 - i0 : Q;
+                if (int rc = src.fill(i0, nr, dT, Q, B, c->stream, true)) return rc;
+                if (skip_last) DPR_HIP(hipMemsetAsync(dT + (B - 1) * Q, 0, sizeof(double) * (size_t)Q, c->stream));
+                if (int rc = dc_assign(r.tab, dT, Q, (int)nr, r.d_cl + i0, c->stream)) return rc;
+            }
+        }
+        if (r.real) {
+            if (int rc = comm_all_reduce_sum(c, r.d_cl, (size_t)n, kNcclInt32, c->stream)) return rc;
+        }
+        DPR_HIP(hipMemcpyAsync(r.h_cl.data(), r.d_cl, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        DPR_HIP(hipEventRecord(r.ev[2], c->stream));
+        return DPR_OK;
+    };
+    const int rc = assign();
+    const hipError_t se = hipStreamSynchronize(c->stream);      // (the stream is idle before the scope releases dT)
+    if (rc) return rc;
+    DPR_HIP(se);
+    for (int64_t t = 0; t < B; ++t) r.h_cl[(size_t)t] = -1;
+    return DPR_OK;
+}
+
+// cluster trees (findClusterTreeDC).  Multi-GPU: clusters are dealt to the ranks; an array element is changed by at most one
+// rank, so the states are merged as old + sum of (new - old) (dc_delta_*).
+static int dc_cluster_trees(DcRun& r)
+{
+    dpr_ctx* c = r.c;
+    const int64_t n = r.n;
+    size_t free_b = 0, total_b = 0;
+    DPR_HIP(hipMemGetInfo(&free_b, &total_b));
+    size_t budget = free_b / 2;
+    if (const char* env = std::getenv("DPR_DC_BUDGET_MB")) budget = (size_t)std::atoll(env) << 20;
+    auto phase = [&](int v) -> int {
+        return dc_cluster_phase(c->place, r.h_cl.data(), n, r.B, r.source, r.dist_type, &c->msa, &c->mash, c->place_trace, budget, &c->dc_stats, v, r.W, c->stream);
+    };
+    if (r.W == 1) return phase(0);
+    const bool real = r.real;
+    auto copy_words = [&](void* dst, const void* src, int64_t words) -> int {
+        DPR_HIP(hipMemcpyAsync(dst, src, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToDevice, c->stream));
+        return DPR_OK;
+    };
+    const auto arrs = dc_arrays(r);
+    const int64_t tot = arrs.back().off + arrs.back().words;
+    DPR_HIP(r.snap_old.alloc((size_t)tot));
+    if (!real) { DPR_HIP(r.snap_acc.alloc((size_t)tot)); DPR_HIP(hipMemsetAsync(r.snap_acc, 0, sizeof(uint64_t) * (size_t)tot, c->stream)); }
+    uint64_t* old = r.snap_old;
+    uint64_t* acc = r.snap_acc;
+    for (const DcArr& a : arrs) { if (int rc = copy_words(old + a.off, a.cur, a.words)) return rc; }
+    if (budget > sizeof(uint64_t) * (size_t)tot * 2) budget -= sizeof(uint64_t) * (size_t)tot * 2;
+    for (int v = 0; v < r.W; ++v) {
+        if (real && v != c->rank) continue;
+        if (!real && v > 0) {                // next virtual rank starts from the backbone state again
+            for (const DcArr& a : arrs) { if (int rc = copy_words(a.cur, old + a.off, a.words)) return rc; }
+        }
+        if (int rc = phase(v)) return rc;
+        for (const DcArr& a : arrs) {
+            if (int rc = dc_delta_sub(a.cur, old + a.off, a.words, c->stream)) return rc;
+            if (!real) { if (int rc = dc_delta_add(acc + a.off, a.cur, a.words, c->stream)) return rc; }
+        }
+    }
+    for (const DcArr& a : arrs) {
+        if (int rc = real ? comm_all_reduce_sum(c, a.cur, (size_t)a.words, kNcclUint64, c->stream) : copy_words(a.cur, acc + a.off, a.words)) return rc;
+        if (int rc = dc_delta_add(a.cur, old + a.off, a.words, c->stream)) return rc;
+    }
+    return DPR_OK;
+}
+
 int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t backbone, int flags, int32_t* head,
                int32_t* e, int32_t* nxt, int32_t* belong, double* len, int32_t* cluster_id)
 {
@@ -458,121 +454,26 @@ int dpr_dc_run(dpr_ctx* c, int source, int dist_type, int k, int64_t n, int64_t 
     }
     if (int rc = check_source(c, "dpr_dc_run", source, k, n)) return rc;
     if (source == DPR_SRC_MSA && c->msa.aa) { set_error("dpr_dc_run: divide-and-conquer is not available for a protein alignment (nucleotide alignments only)"); return DPR_ERR_ARG; }
-    const int64_t B = backbone;
-    if (int rc = rebuild_place(c, n, B)) return rc;
-    PlaceBuffers& p = c->place;
+    if (int rc = rebuild_place(c, n, backbone)) return rc;
     if (int rc = reset_place_trace(c, n)) return rc;
-    ScopedEvent ev[4];
-    for (auto& x : ev) DPR_HIP(hipEventCreate(x.put()));
-    DevBuf<int32_t> d_cl;
-    DevBuf<double> dT;
-    DevBuf<uint64_t> snap_old, snap_acc;
-    DcTable tab;
-    struct TableGuard { DcTable& t; ~TableGuard() { dc_table_free(t); } } tab_guard{ tab };
-    const RowSource src{ c, source, dist_type };
-    // ranks: RCCL ranks of dpr_comm_init, or -- validation on one GPU -- DPR_DC_VIRTUAL_RANKS(w) emulated in turn
-    const bool real = comm_real(c);
-    const int W = real ? c->world : (((flags >> 8) & 0xff) > 1 ? ((flags >> 8) & 0xff) : 1);
-    std::vector<int32_t> h_cl((size_t)n, -1);
-    auto run = [&]() -> int {
-        // ---- backbone tree: tips [0, B) (findBackboneTreeDC)
-        DPR_HIP(hipEventRecord(ev[0], c->stream));
-        if (int rc = place_range(c, source, dist_type, 2, B)) return rc;
-        DPR_HIP(hipEventRecord(ev[1], c->stream));
-        // ---- cluster assignment of tips [B, n) (findClustersDC).  Multi-GPU: the backbone above is built
-        // identically on every rank (same inputs, deterministic kernels); the queries are independent, so each
-        // rank assigns a contiguous share and the ids are summed (zeros elsewhere) over RCCL.
-        if (int rc = dc_table_build(p, B, tab, c->stream)) return rc;
-        int64_t Q = ((int64_t)1 << 31) / (8 * B) / 256 * 256;
-        if (Q < 256) Q = 256;
-        if (Q > 8192) Q = 8192;
-        const int64_t nq = n - B;
-        if (Q > (nq + 255) / 256 * 256) Q = (nq + 255) / 256 * 256;
-        DPR_HIP(dT.alloc((size_t)(B * Q)));
-        DPR_HIP(d_cl.alloc((size_t)(n + 1)));
-        DPR_HIP(hipMemsetAsync(d_cl, 0, sizeof(int32_t) * (size_t)(n + 1), c->stream));
-        // the reference's aligned-input kernel never writes the distance to backbone tip B-1
-        // (src/divide_and_conquer/msa.cu:331 `idx>=ed-st`) and scans the 0.0 of a fresh allocation
-        const bool skip_last = source == DPR_SRC_MSA && !(flags & DPR_DC_EXACT_LAST);
-        for (int v = 0; v < W; ++v) {
-            if (real && v != c->rank) continue;     // virtual ranks: every share is processed here, one after the other
-            int64_t q0 = 0, q1 = 0;
-            dc_query_share(n, B, v, W, &q0, &q1);
-            for (int64_t i0 = q0; i0 < q1; i0 += Q) {
-                const int64_t nr = q1 - i0 < Q ? q1 - i0 : Q;
-                if (int rc = src.fill(i0, nr, dT, Q, B, c->stream, true)) return rc;
-                if (skip_last) DPR_HIP(hipMemsetAsync(dT + (B - 1) * Q, 0, sizeof(double) * (size_t)Q, c->stream));
-                if (int rc2 = dc_assign(tab, dT, Q, (int)nr, d_cl + i0, c->stream)) return rc2;
-            }
-        }
-        if (real) {
-            if (int rc = comm_all_reduce_sum(c, d_cl, (size_t)n, kNcclInt32, c->stream)) return rc;
-        }
-        DPR_HIP(hipMemcpyAsync(h_cl.data(), d_cl, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        DPR_HIP(hipEventRecord(ev[2], c->stream));
-        DPR_HIP(hipStreamSynchronize(c->stream));
-        for (int64_t t = 0; t < B; ++t) h_cl[(size_t)t] = -1;
-        dT.reset();                 // (before the budget below is read)
-        // ---- cluster trees (findClusterTreeDC).  Multi-GPU: clusters are dealt to the ranks; an array element
-        // is changed by at most one rank, so the states are merged as old + sum of (new - old) (dc_delta_*).
-        size_t free_b = 0, total_b = 0;
-        DPR_HIP(hipMemGetInfo(&free_b, &total_b));
-        size_t budget = free_b / 2;
-        if (const char* env = std::getenv("DPR_DC_BUDGET_MB")) budget = (size_t)std::atoll(env) << 20;
-        if (W == 1) {
-            if (int rc = dc_cluster_phase(p, h_cl.data(), n, B, source, dist_type, &c->msa, &c->mash, c->place_trace, budget,
-                                          &c->dc_stats, 0, 1, c->stream)) return rc;
-        } else {
-            struct Arr { void* cur; int64_t words; };
-            const Arr arrs[] = { { p.head, n }, { p.e, 4 * n }, { p.nxt, 4 * n }, { p.belong, 4 * n }, { p.rev, 4 * n },
-                                 { p.len, 8 * n }, { p.cid, 20 * n }, { p.cdis, 40 * n }, { c->place_trace, 3 * n } };
-            int64_t tot = 0;
-            for (const Arr& a : arrs) tot += a.words;
-            DPR_HIP(snap_old.alloc((size_t)tot));
-            if (!real) { DPR_HIP(snap_acc.alloc((size_t)tot)); DPR_HIP(hipMemsetAsync(snap_acc, 0, sizeof(uint64_t) * (size_t)tot, c->stream)); }
-            int64_t off = 0;
-            for (const Arr& a : arrs) { DPR_HIP(hipMemcpyAsync(snap_old + off, a.cur, sizeof(uint64_t) * (size_t)a.words, hipMemcpyDeviceToDevice, c->stream)); off += a.words; }
-            if (budget > sizeof(uint64_t) * (size_t)tot * 2) budget -= sizeof(uint64_t) * (size_t)tot * 2;
-            for (int v = 0; v < W; ++v) {
-                if (real && v != c->rank) continue;
-                if (!real && v > 0) {                // next virtual rank starts from the backbone state again
-                    off = 0;
-                    for (const Arr& a : arrs) { DPR_HIP(hipMemcpyAsync(a.cur, snap_old + off, sizeof(uint64_t) * (size_t)a.words, hipMemcpyDeviceToDevice, c->stream)); off += a.words; }
-                }
-                if (int rc = dc_cluster_phase(p, h_cl.data(), n, B, source, dist_type, &c->msa, &c->mash, c->place_trace, budget,
-                                              &c->dc_stats, v, W, c->stream)) return rc;
-                off = 0;
-                for (const Arr& a : arrs) {
-                    if (int rc = dc_delta_sub(a.cur, snap_old + off, a.words, c->stream)) return rc;
-                    if (!real) { if (int rc = dc_delta_add(snap_acc + off, a.cur, a.words, c->stream)) return rc; }
-                    off += a.words;
-                }
-            }
-            off = 0;
-            for (const Arr& a : arrs) {
-                if (real) {
-                    if (int rc = comm_all_reduce_sum(c, a.cur, (size_t)a.words, kNcclUint64, c->stream)) return rc;
-                } else {
-                    DPR_HIP(hipMemcpyAsync(a.cur, snap_acc + off, sizeof(uint64_t) * (size_t)a.words, hipMemcpyDeviceToDevice, c->stream));
-                }
-                if (int rc = dc_delta_add(a.cur, snap_old + off, a.words, c->stream)) return rc;
-                off += a.words;
-            }
-        }
-        DPR_HIP(hipEventRecord(ev[3], c->stream));
-        if (int rc = copy_adjacency(c, n, false, head, e, nxt, belong, len)) return rc;
-        DPR_HIP(hipStreamSynchronize(c->stream));
-        float ms = 0;
-        DPR_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); c->dc_ms[0] = ms;
-        DPR_HIP(hipEventElapsedTime(&ms, ev[1], ev[2])); c->dc_ms[1] = ms;
-        DPR_HIP(hipEventElapsedTime(&ms, ev[2], ev[3])); c->dc_ms[2] = ms;
-        c->nj_ms = c->dc_ms[0] + c->dc_ms[1] + c->dc_ms[2];
-        if (cluster_id) std::copy(h_cl.begin(), h_cl.end(), cluster_id);
-        return DPR_OK;
-    };
-    const int rc = run();
-    place_collect_dist_ms(c);     // (backbone placement batches; the events must not outlive the run)
-    return rc;
+    const int vw = (flags >> 8) & 0xff;
+    DcRun r{ c, source, dist_type, flags, n, backbone, comm_real(c), 1 };
+    r.W = r.real ? c->world : (vw > 1 ? vw : 1);
+    r.h_cl.assign((size_t)n, -1);
+    for (auto& x : r.ev) DPR_HIP(hipEventCreate(x.put()));
+    if (int rc = dc_backbone(r)) return rc;
+    if (int rc = dc_assign_queries(r)) return rc;
+    if (int rc = dc_cluster_trees(r)) return rc;
+    DPR_HIP(hipEventRecord(r.ev[3], c->stream));
+    if (int rc = copy_adjacency(c, n, false, head, e, nxt, belong, len)) return rc;
+    DPR_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    DPR_HIP(hipEventElapsedTime(&ms, r.ev[0], r.ev[1])); c->dc_ms[0] = ms;
+    DPR_HIP(hipEventElapsedTime(&ms, r.ev[1], r.ev[2])); c->dc_ms[1] = ms;
+    DPR_HIP(hipEventElapsedTime(&ms, r.ev[2], r.ev[3])); c->dc_ms[2] = ms;
+    c->nj_ms = c->dc_ms[0] + c->dc_ms[1] + c->dc_ms[2];
+    if (cluster_id) std::copy(r.h_cl.begin(), r.h_cl.end(), cluster_id);
+    return DPR_OK;
 }
 
 int dpr_dc_query_share(int64_t n, int64_t backbone, int rank, int world, int64_t* q0, int64_t* q1)
@@ -685,12 +586,7 @@ int dpr_place_fixed_run(dpr_ctx* c, int source, int dist_type, int k, int32_t* s
     const int64_t share = ((nq + W - 1) / W + 255) / 256 * 256;
     int64_t q0 = 0, q1 = 0;
     dc_query_share(n, m, rank, W, &q0, &q1);
-    // queries per batch: the rule of dpr_dc_run (the block of distances to all backbone tips stays below 2 GiB)
-    int64_t Q = ((int64_t)1 << 31) / (8 * m) / 256 * 256;
-    if (Q < 256) Q = 256;
-    if (Q > 8192) Q = 8192;
-    if (Q > (nq + 255) / 256 * 256) Q = (nq + 255) / 256 * 256;
-    if (f.batch > 0) Q = f.batch;
+    const int64_t Q = f.batch > 0 ? f.batch : query_batch(m, nq);      // (dpr_ctx_set_place_fixed_batch overrides the rule)
     if ((size_t)(m * Q) > f.dT_cap) {
         if (f.dT) { (void)hipFree(f.dT); f.dT = nullptr; f.dT_cap = 0; }
         DPR_HIP(hipMalloc(&f.dT, sizeof(double) * (size_t)(m * Q)));

@@ -419,6 +419,26 @@ int dpr_get_place_overlap(dpr_ctx *ctx, int *overlapped, double *dist_busy_ms);
  * one row per tip, serially).  *batches / *overlapped_batches of the last placement run.  DPR_PLACE_NO_OVERLAP=1: never,
  * DPR_PLACE_OVERLAP_ALWAYS=1: round 3's policy (every batch).  Results do not depend on it. */
 int dpr_get_place_policy(dpr_ctx *ctx, int64_t *batches, int64_t *overlapped_batches);
+/* Host-only, pure (no device, no environment): the per-batch overlap policy of dpr_place_run (csrc/place_policy.hpp) run over a
+ * described placement of tips [first, last).  world: real ranks; window_transport: they are joined by dpr_comm_init_shared (no
+ * RCCL communicator); no_overlap: DPR_PLACE_NO_OVERLAP is set; multi_min: first tip of the four-tip launches
+ * (DPR_PLACE_MULTI_MIN, default 150 000); batch_rows: DPR_PLACE_BATCH, outside [16, 65536] = the source's default R (1024 for
+ * Mash, 256 otherwise).  Batch b is [i0, i0 + nr), i0 = first + b * R; tree_ms[b] and dist_alone_ms[b] are what the event pairs
+ * around its tree kernels and -- were its rows produced alone on the main stream -- around its rows would report.
+ * `batches` must be ceil((last - first) / R).  beside[b] = 1 if batch b is produced beside batch b - 1's tree kernels.  The rule:
+ *   fixed for a run     allowed = Mash source, no_overlap unset, not (world > 1 on the window transport, whose all-gather is
+ *                       synchronous with the host); always = allowed and world > 1
+ *   pairs(i0, nr)       nr * (i0 + 0.5 * (nr - 1))
+ *   learned             tree_ms_per_tip = -1 and pairs_per_ms = 4.5e6 at the start.  Observing a finished batch:
+ *                       tree_ms_per_tip = tree_ms / nr / (its tree kernels ran alone ? 1 : 1.4); if its rows were produced alone,
+ *                       its pairs are >= 5e7 and dist_alone_ms > 0: pairs_per_ms = pairs / dist_alone_ms.  In order, latest wins.
+ *   successor [j0, j0 + nr2) of batch [i0, i0 + nr), j0 = i0 + R:
+ *                       not allowed, or j0 >= last: no.  always, or i0 + nr <= multi_min: yes.  Otherwise every batch before
+ *                       the current one is observed, est = pairs(j0, nr2) / pairs_per_ms, and the answer is
+ *                       est < tree_ms_per_tip * nr once tree_ms_per_tip > 0, est < 1.0 before that.
+ * Only the last case reads timings (there dpr_place_run's host waits for batch b - 1, and no further). */
+int dpr_place_policy_run(int source, int world, int window_transport, int no_overlap, int64_t multi_min, int64_t first, int64_t last,
+                         int64_t batch_rows, const double *tree_ms, const double *dist_alone_ms, int64_t batches, int32_t *beside);
 
 /* Per placed tip of the last placement run: slots its closest-list walk reached (updateClosestNodes, src/placement_close_k.cu:
  * 86-124) beyond the two rounds applied with the split; negative = -(reached + 1): the walk of a node of degree > 3 (imported

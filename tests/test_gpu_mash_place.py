@@ -180,6 +180,46 @@ def test_placement_msa_and_mash_sources(gpu, orc, monkeypatch, multi):
     _same_state(got, orc.place_run(M), len(reads))
 
 
+def test_placement_many_small_batches(gpu, orc, monkeypatch):
+    """300 reads in batches of 16 rows: 19 batches, the last one short, both row buffers reused many times.  Every batch beside
+    the previous one's tree kernels (default), none (DPR_PLACE_NO_OVERLAP), and the timed rule on the four-tip launches
+    (DPR_PLACE_MULTI_MIN=3, whose decisions depend on timings and are not asserted): the oracle's adjacency, lists and trace bit for
+    bit each time.  The default and the no-overlap run are then repeated on the same context: each reports its own batches and
+    timings, nothing of the runs before.  Events carried over from an earlier run would add at least that whole run's figure, i.e.
+    double it; the bound is 1.5 x the first run's, which had the cold start on its side."""
+    from dipper_amd import capi
+    reads = _reads(np.random.default_rng(123), 300, 3000, 6000)
+    n = len(reads)
+    gpu.set_reads(reads)
+    gpu.sketch(k=15, S=1000, fetch=False)
+    gpu.dist_matrix(capi.SRC_MASH, 0, 15)
+    ref = orc.place_run(gpu.matrix())
+    monkeypatch.setenv("DPR_PLACE_BATCH", "16")
+    seen = {}
+    for mode in ("default", "no-overlap", "timed", "default again", "no-overlap again"):
+        with monkeypatch.context() as mp:
+            if mode.startswith("no-overlap"):
+                mp.setenv("DPR_PLACE_NO_OVERLAP", "1")
+            if mode == "timed":
+                mp.setenv("DPR_PLACE_MULTI_MIN", "3")
+            got = gpu.place_run(capi.SRC_MASH, n, k=15)
+        _same_state(got, ref, n)
+        batches, beside = gpu.place_policy()
+        overlapped, busy_ms = gpu.place_overlap()
+        dist_ms, tree_ms = gpu.place_timing()
+        run_ms = gpu.timing()[1]
+        seen[mode] = figures = dict(batches=batches, beside=beside, overlapped=overlapped, busy_ms=busy_ms, dist_ms=dist_ms, tree_ms=tree_ms, run_ms=run_ms)
+        assert batches == 19, (mode, figures)
+        if mode.startswith("default"):
+            assert (beside, overlapped) == (18, True), (mode, figures)
+        if mode.startswith("no-overlap"):
+            assert (beside, overlapped, busy_ms) == (0, False, 0.0), (mode, figures)
+        if mode.endswith("again"):
+            first = seen[mode[:-len(" again")]]
+            assert dist_ms + tree_ms == pytest.approx(run_ms, rel=1e-9) and tree_ms > 0.0, (mode, figures)
+            assert 0.0 < dist_ms < 1.5 * first["dist_ms"] and busy_ms <= 1.5 * first["busy_ms"], (mode, figures, first)
+
+
 def test_placement_repeatable_in_both_launch_shapes(monkeypatch):
     """the edge split is shared by two wavefronts of the update launch (place_split_wave): one must not overwrite what the other still
     reads.  30 000 tips three times per launch shape (one tip per launch pair; four per pair from tip 64 on): every trace bit-equal
