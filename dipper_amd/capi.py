@@ -154,6 +154,12 @@ def load_library():
     L.dpr_split_support.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]
     L.dpr_comm_sum_i32.argtypes = [C.c_void_p, c_i32p, C.c_int64]
     L.dpr_transfer_support.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
+    _bme_out = [C.c_int, c_i32p, c_i32p, c_f64p, c_f64p, c_i64p]
+    L.dpr_bme_nni.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p] + _bme_out
+    L.dpr_bme_nni_host.argtypes = [c_f64p, C.c_int64, c_i32p, c_i32p] + _bme_out
+    L.dpr_bme_eval_host.argtypes = [c_f64p, C.c_int64, c_i32p, C.c_int32, c_f64p, c_f64p, c_i32p, c_f64p]
+    L.dpr_get_bme_timing.argtypes = [C.c_void_p, c_f64p, c_f64p]
+    L.dpr_get_bme_stats.argtypes = [C.c_void_p, c_i64p]
     L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
     L.dpr_transfer_taxa.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
@@ -354,6 +360,50 @@ def transfer_taxa_host(n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi
     _chk(lib, lib.dpr_transfer_taxa_host(n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p), cutoff_permille,
                                          _p(phi_sum, c_i64p), _p(moved, c_i64p), _p(pairs, c_i64p)))
     return phi_sum, moved, pairs
+
+
+def _bme_args(n, merge_x, merge_y, max_rounds):
+    mx, my = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)[: max(n - 2, 0)]) for a in (merge_x, merge_y))
+    assert len(mx) == len(my) == n - 2
+    out = dict(kids=np.zeros(2 * max(n - 2, 1), dtype=np.int32), top=np.zeros(1, dtype=np.int32), len=np.zeros(2 * n - 2, dtype=np.float64),
+               L_rounds=np.zeros(max_rounds + 1, dtype=np.float64), stats=np.zeros(4, dtype=np.int64))
+    ptrs = (_p(mx, c_i32p), _p(my, c_i32p), max_rounds, _p(out["kids"], c_i32p), _p(out["top"], c_i32p), _p(out["len"], c_f64p),
+            _p(out["L_rounds"], c_f64p), _p(out["stats"], c_i64p))
+    return (mx, my), out, ptrs
+
+
+def _bme_result(n, out):
+    rounds, moves, fallbacks, cands0 = (int(v) for v in out["stats"])
+    return dict(kids=out["kids"][: 2 * (n - 2)].reshape(n - 2, 2), top=int(out["top"][0]), len=out["len"], L_rounds=out["L_rounds"][: rounds + 1],
+                rounds=rounds, moves=moves, fallbacks=fallbacks, candidates0=cands0)
+
+
+def bme_nni_host(D, merge_x, merge_y, max_rounds):
+    """Balanced minimum evolution NNI search restated on the host (no GPU).  D: (n, n) array whose strict lower triangle is read;
+    merge_x / merge_y: a merge log of n - 2 entries.  dict(kids (n-2, 2): children of node n+k hung from tip n-1; top: the node
+    next to tip n-1; len (2n-2): balanced length of the edge above every node; L_rounds: the tree length before and after every
+    accepted round; rounds, moves, fallbacks, candidates0)"""
+    lib = load_library()
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    rows = np.ascontiguousarray(np.concatenate([D[i, :i] for i in range(n)])) if n > 1 else np.zeros(1)
+    keep, out, ptrs = _bme_args(n, merge_x, merge_y, max_rounds)
+    _chk(lib, lib.dpr_bme_nni_host(_p(rows, c_f64p), n, *ptrs))
+    return _bme_result(n, out)
+
+
+def bme_eval_host(D, kids, top):
+    """one evaluation of the tree (kids, top) as bme_nni_host returns it (host only): dict(len, gain, move, L), 2n-2 entries each"""
+    lib = load_library()
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    rows = np.ascontiguousarray(np.concatenate([D[i, :i] for i in range(n)]))
+    kids = np.ascontiguousarray(np.asarray(kids, dtype=np.int32).reshape(-1))
+    assert len(kids) == 2 * (n - 2)
+    ln, gain, move = np.zeros(2 * n - 2), np.zeros(2 * n - 2), np.zeros(2 * n - 2, dtype=np.int32)
+    L = C.c_double(0.0)
+    _chk(lib, lib.dpr_bme_eval_host(_p(rows, c_f64p), n, _p(kids, c_i32p), int(top), _p(ln, c_f64p), _p(gain, c_f64p), _p(move, c_i32p), C.byref(L)))
+    return dict(len=ln, gain=gain, move=move, L=L.value)
 
 
 NJ_VARIANT_NJ, NJ_VARIANT_BIONJ = 0, 1
@@ -826,6 +876,26 @@ class Dipper:
         _chk(self.L, self.L.dpr_transfer_support(self.h, n, _p(mx, c_i32p), _p(my, c_i32p), _p(rx, c_i32p), _p(ry, c_i32p),
                                                  _p(phi_sum, c_i64p)))
         return phi_sum
+
+    def bme_nni(self, merge_x, merge_y, max_rounds):
+        """bme_nni_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run)"""
+        n = len(np.asarray(merge_x)) + 2
+        keep, out, ptrs = _bme_args(n, merge_x, merge_y, max_rounds)
+        _chk(self.L, self.L.dpr_bme_nni(self.h, n, *ptrs))
+        return _bme_result(n, out)
+
+    def bme_timing(self):
+        """(table ms, lengths + gains ms) of the last bme_nni, summed over its evaluations"""
+        a = C.c_double()
+        b = C.c_double()
+        _chk(self.L, self.L.dpr_get_bme_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def bme_stats(self):
+        """dict(table_bytes, allocations so far, launches and evaluations of the last bme_nni)"""
+        out = np.zeros(4, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_bme_stats(self.h, _p(out, c_i64p)))
+        return dict(table_bytes=int(out[0]), allocations=int(out[1]), launches=int(out[2]), evaluations=int(out[3]))
 
     def transfer_taxa(self, n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi_sum=None, moved=None, pairs=None):
         """transfer_taxa_host's numbers, computed on the device"""

@@ -450,6 +450,19 @@ struct TbeBuffers {
 };
 void tbe_free(TbeBuffers& t);
 
+// ---- balanced minimum evolution NNI (bme.hip) ------------------------------------------------------------------------------------
+// Kept by the context from the first dpr_bme_nni on (a later call over no more tips allocates nothing); released with it.
+struct BmeBuffers {
+    DevBuf<double> T;                    // [M][ld] table of subtree averages over the M = 2n - 2 nodes (S and W, see bme_host.hpp), by place in rank order
+    DevBuf<int32_t> itab;                // [9][ldi]: kid0, kid1, par, sib, height, tin, tout, rows, pos (place of a node in T)
+    DevBuf<double> out;                  // [2][ldi]: length of the edge above every node, gain
+    DevBuf<int32_t> omove;               // [ldi] candidate move of every node (0: none)
+    int64_t cap_n = 0, ld = 0, ldi = 0;  // tips the buffers hold, row stride of T, stride of the small arrays
+    int64_t allocations = 0;             // device allocations made for this context so far
+    int64_t launches = 0, evaluations = 0;       // kernels / table builds of the last call
+    double table_ms = 0, select_ms = 0;  // of the last call: table (fill, S, W) / lengths + gains and their copy back (HIP events)
+};
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of 512 tips the (value -> tips, positions) postings
 struct MashIndex {

@@ -211,6 +211,29 @@ void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<st
     }
 }
 
+void NJDeviceArrays::findRefinedTree(DeviceContext& dev, Param& params, MatrixReader* matrixReader, std::vector<std::string>& name,
+                                     std::ostream& output_, int rounds)
+{
+    const int N = d_numSequences;
+    std::vector<int32_t> mx((size_t)std::max(N - 2, 1)), my((size_t)std::max(N - 2, 1));
+    const int64_t done = dpr_nj_run(dev.ctx, -1, mx.data(), my.data(), nullptr, nullptr, nullptr);
+    if (done < 0) gpuCheck((int)done, "dpr_nj_run");
+    getDismatrix(dev, N, params, matrixReader);      // (the NJ run consumed the matrix: the search reads a fresh one)
+    std::vector<int32_t> kids((size_t)(2 * std::max(N - 2, 1)));
+    std::vector<double> len((size_t)(2 * N - 2)), L((size_t)rounds + 1, 0.0);
+    int32_t top = 0;
+    int64_t stats[4] = { 0, 0, 0, 0 };
+    gpuCheck(dpr_bme_nni(dev.ctx, N, mx.data(), my.data(), rounds, kids.data(), &top, len.data(), L.data(), stats), "dpr_bme_nni");
+    writeNewickFromKids(output_, name, kids, top, len);
+    std::cerr << "BME NNI: L " << L[0] << " -> " << L[(size_t)stats[0]] << ", " << stats[1] << " moves, " << stats[0] << " rounds, " << stats[2]
+              << " fallbacks\n";
+    if (cliLog()) {
+        double table_ms = 0, select_ms = 0;
+        dpr_get_bme_timing(dev.ctx, &table_ms, &select_ms);
+        std::cerr << "  device: BME tables " << table_ms << " ms, lengths and gains " << select_ms << " ms\n";
+    }
+}
+
 void packUnaligned(const std::vector<std::string>& seqs, const std::vector<int>& ids, std::vector<uint64_t>& flat,
                    std::vector<uint64_t>& off, std::vector<uint64_t>& lens)
 {

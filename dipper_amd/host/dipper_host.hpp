@@ -167,6 +167,10 @@ struct NJDeviceArrays {  // src/mash_placement.cuh:199-212
     int d_numSequences = 0;
     void getDismatrix(DeviceContext& dev, int numSequences, Param& params, MatrixReader* matrixReader);
     void findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_);
+    // --nni R: the NJ / BIONJ tree as above, the distance matrix built again, at most R rounds of balanced minimum evolution NNI
+    // on it (dpr_bme_nni) and the tree it ends on with its balanced branch lengths; one line on stderr
+    void findRefinedTree(DeviceContext& dev, Param& params, MatrixReader* matrixReader, std::vector<std::string>& name, std::ostream& output_,
+                         int rounds);
 };
 
 struct MashDeviceArrays {  // src/mash_placement.cuh:34-50
@@ -273,6 +277,11 @@ inline bool cliLog()
 void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
                            const std::vector<int32_t>& my, const std::vector<double>& bx,
                            const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels = nullptr);
+
+// Newick text of a tree as dpr_bme_nni returns it (--nni): kid holds the two children of internal node N+k, len the edge above
+// every node; the root joins name[N-1] and `top`, each with half of len[top], as the NJ writer halves its last edge
+void writeNewickFromKids(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& kid, int32_t top,
+                         const std::vector<double>& len);
 
 // ---- bootstrap support (support.cpp; no reference counterpart) -----------------------------------------------------------
 struct BootstrapOptions {

@@ -617,9 +617,12 @@ void MatrixReader::read(const std::string& path)
     }
 }
 
-void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
-                           const std::vector<int32_t>& my, const std::vector<double>& bx,
-                           const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels)
+namespace {
+struct Child { int node; double len; };
+// the binary tree below `root` (kids: two children per internal node, tips < N) as Newick text, iterative pre-order:
+// "(" child ":" len "," child ":" len ")"
+void writeBinaryNewick(std::ostream& os, const std::vector<std::string>& name, const std::vector<Child>& kids, int root,
+                       const std::vector<int32_t>* labels)
 {
     const int N = (int)name.size();
     // the `)` that closes internal node `node` (never the root: its `)` is followed by ';')
@@ -631,22 +634,6 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
             out.s.append(b, (size_t)(r.ptr - b));
         }
     };
-    struct Child { int node; double len; };
-    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });  // two children per internal node
-    std::vector<int> realID((size_t)N);
-    for (int i = 0; i < N; ++i) realID[(size_t)i] = i;
-    int ID = N;
-    for (int it = 0; it < N - 2; ++it) {
-        const int x = mx[(size_t)it], y = my[(size_t)it];
-        kids[(size_t)ID * 2] = Child{ realID[(size_t)x], bx[(size_t)it] };
-        kids[(size_t)ID * 2 + 1] = Child{ realID[(size_t)y], by[(size_t)it] };
-        realID[(size_t)x] = ID++;
-        realID[(size_t)y] = realID[(size_t)(N - it - 1)];
-    }
-    const int root = 2 * N - 2;
-    kids[(size_t)root * 2] = Child{ realID[0], last_d * 0.5 };
-    kids[(size_t)root * 2 + 1] = Child{ realID[1], last_d * 0.5 };
-    // iterative pre-order print: "(" child ":" len "," child ":" len ")"
     struct Frame { int node; int next; };
     std::vector<Frame> st;
     st.push_back(Frame{ root, 0 });
@@ -676,6 +663,45 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
     }
     out.put(";\n");
     os.write(out.s.data(), (std::streamsize)out.s.size());
+}
+}  // namespace
+
+void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
+                           const std::vector<int32_t>& my, const std::vector<double>& bx,
+                           const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels)
+{
+    const int N = (int)name.size();
+    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });  // two children per internal node
+    std::vector<int> realID((size_t)N);
+    for (int i = 0; i < N; ++i) realID[(size_t)i] = i;
+    int ID = N;
+    for (int it = 0; it < N - 2; ++it) {
+        const int x = mx[(size_t)it], y = my[(size_t)it];
+        kids[(size_t)ID * 2] = Child{ realID[(size_t)x], bx[(size_t)it] };
+        kids[(size_t)ID * 2 + 1] = Child{ realID[(size_t)y], by[(size_t)it] };
+        realID[(size_t)x] = ID++;
+        realID[(size_t)y] = realID[(size_t)(N - it - 1)];
+    }
+    const int root = 2 * N - 2;
+    kids[(size_t)root * 2] = Child{ realID[0], last_d * 0.5 };
+    kids[(size_t)root * 2 + 1] = Child{ realID[1], last_d * 0.5 };
+    writeBinaryNewick(os, name, kids, root, labels);
+}
+
+void writeNewickFromKids(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& kid, int32_t top,
+                         const std::vector<double>& len)
+{
+    const int N = (int)name.size();
+    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });
+    for (int k = 0; k < N - 2; ++k)
+        for (int s = 0; s < 2; ++s) {
+            const int32_t c = kid[(size_t)(2 * k + s)];
+            kids[(size_t)(N + k) * 2 + (size_t)s] = Child{ c, len[(size_t)c] };
+        }
+    const int root = 2 * N - 2;
+    kids[(size_t)root * 2] = Child{ N - 1, len[(size_t)top] * 0.5 };
+    kids[(size_t)root * 2 + 1] = Child{ top, len[(size_t)top] * 0.5 };
+    writeBinaryNewick(os, name, kids, root, nullptr);
 }
 
 }  // namespace dipper

@@ -88,6 +88,13 @@ static const char* kHelp =
     "                              builds the tree (-m 2, or -m 0 below 30000; -i d, m or r; --protein;\n"
     "                              every -d); with --bootstrap the main tree and every replicate tree are\n"
     "                              BIONJ trees.  Not with -m 1, -m 3, --add, -o d or -o j\n"
+    "  --nni arg                   Refine the NJ / BIONJ tree by nearest-neighbour interchanges under balanced\n"
+    "                              minimum evolution (Desper & Gascuel 2002): at most arg >= 0 rounds, each\n"
+    "                              applying every improving interchange that shares no node with a better\n"
+    "                              one; the tree is written with its balanced branch lengths (arg 0: those of\n"
+    "                              the NJ topology).  Wherever conventional NJ builds the tree (-m 2, or -m 0\n"
+    "                              below 30000; -i d, m or r; --protein; --bionj; every -d); one GPU.  Not\n"
+    "                              with -m 1, -m 3, --add, -o d, -o j, --bootstrap or several ranks\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -116,7 +123,7 @@ static const Opt kOpts[] = {
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
-    { "bionj", 0, false },
+    { "bionj", 0, false }, { "nni", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -302,6 +309,19 @@ int main(int argc, char** argv)
         if (out == "d" || out == "j") usageError("--bionj needs tree output (-o t)");
         bionjOption() = true;      // every context of this command builds BIONJ trees (DeviceContext, the bootstrap's rank-local one)
     }
+    // --nni: what the arguments alone decide, before any input is read or a GPU touched (several ranks: below, once they are parsed)
+    int nni = -1;
+    if (vm.count("nni")) {
+        const std::string nv = vm["nni"], al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
+        bool digits = !nv.empty() && nv.size() <= 9;
+        for (char ch : nv) digits = digits && std::isdigit((unsigned char)ch);
+        if (!digits) usageError("--nni: the number of rounds must be a whole number >= 0");
+        nni = std::stoi(nv);
+        if (al == "1" || al == "3") usageError("--nni needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add")) usageError("--nni is not supported with --add");
+        if (out == "d" || out == "j") usageError("--nni needs tree output (-o t)");
+        if (vm.count("bootstrap")) usageError("--nni is not supported with --bootstrap (replicate trees are not refined)");
+    }
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
     // --protein: what the arguments alone decide, before any input is read or a GPU touched
@@ -420,6 +440,8 @@ int main(int argc, char** argv)
             usageError("--world needs --rank (0 <= rank < world) and --rendezvous");
     }
     const bool multi = ranks.multi();
+    if (nni >= 0 && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
+        usageError("--nni runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
     if (!multi && ranks.devices.size() == 1) device = ranks.devices[0];      // (`--devices 3` alone: one rank on GPU 3)
 
     const int placement_thr = 30000, dc_thr = 1000000;  // src/tree_generation.cu:247-248
@@ -662,6 +684,9 @@ int main(int argc, char** argv)
         if (bionj && pick_mode((long long)numSequences) != 2)
             die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (nni >= 0 && pick_mode((long long)numSequences) != 2)
+            die("ERROR: --nni needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (protein && pick_mode((long long)numSequences) == 3)
             die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
                 " sequences select it in the default mode; use -m 1 or -m 2");
@@ -742,6 +767,8 @@ int main(int argc, char** argv)
                 if (!packed.ok && rankInfo().world > 1) packAligned(seqs, ids, flat, seqLen);
                 bootstrapNeighbourJoiningTree(dev, (int)numSequences, params, boot, packed.ok ? packed.flat.data() : flat.data(),
                                               seqLen, names, *output_);
+            } else if (nni >= 0) {
+                njDeviceArrays.findRefinedTree(dev, params, nullptr, names, *output_, nni);
             } else {
                 njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
             }
@@ -772,6 +799,9 @@ int main(int argc, char** argv)
         if (bionj && mode != 2)
             die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (nni >= 0 && mode != 2)
+            die("ERROR: --nni needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (mode == 3) { std::cerr << "Divide-and-conquer mode not supported with input matrix\n"; return 1; }
         if (multi) startRanks(ranks, device);
         auto output_ = open_out();
@@ -790,7 +820,8 @@ int main(int argc, char** argv)
                 std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
             NJDeviceArrays njDeviceArrays;
             njDeviceArrays.getDismatrix(dev, numSequences, params, &matrixReader);
-            njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_);
+            if (nni >= 0) njDeviceArrays.findRefinedTree(dev, params, &matrixReader, matrixReader.name, *output_, nni);
+            else njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_);
         }
         printRankSummary(dev.ctx);
     } else {

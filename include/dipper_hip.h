@@ -576,6 +576,62 @@ int dpr_ctx_set_tbe_lds(dpr_ctx *ctx, int64_t bytes);
 /* in-place sum of `count` host 64-bit integers over the context's ranks; nothing to do with one rank */
 int dpr_comm_sum_i64(dpr_ctx *ctx, int64_t *host_inout, int64_t count);
 
+/* ---- balanced minimum evolution: NNI refinement of an NJ / BIONJ tree and its balanced branch lengths (Desper & Gascuel 2002;
+ * no reference counterpart: the reference stops at the NJ tree) ----------------------------------------------------------------
+ * Arithmetic contract (fp64, exactly this order of operations, no contraction; the device and dpr_bme_nni_host produce the same
+ * bits).
+ * Tree.  Tips are 0 .. n-1; internal node n+k is the node made by merge k of a merge log (the realID bookkeeping of
+ *   writeNewickFromMerges), k < n-2; the last two nodes of the log are joined by one edge.  The tree is unrooted; for every
+ *   definition it is hung from tip t0 = n-1, which gives parent(v), two children per internal node (c0(v) < c1(v) by id) and
+ *   sib(v).  t0 has one neighbour c; t0 counts as a tip that is nobody's ancestor.  height(tip) = 0, height(v) = 1 + max over
+ *   the children; rank(v) = (height, id).
+ * Averages.  S(u,v) = S(v,u), for u != v where neither is an ancestor of the other: both tips (t0 included): the matrix entry
+ *   D[u][v]; otherwise, u being the node of larger rank, S = 0.5 * (S(c0(u),v) + S(c1(u),v)).
+ *   W(u,v), for v a proper ancestor of u, v != t0 (the average between the clade of u and everything outside the clade of v):
+ *   parent(v) = t0: W = S(u,t0); otherwise W = 0.5 * (S(u,sib(v)) + W(u,parent(v))).
+ * Length of the edge above v, p = parent(v):
+ *   v = c, children A, B:               0.5 * ((S(A,t0) + S(B,t0)) - S(A,B))       (also the pendant edge of t0)
+ *   v a tip, C = sib(v):                0.5 * ((S(v,C) + W(v,p)) - W(C,p))
+ *   v internal, A = c0(v), B = c1(v), C = sib(v):
+ *                                       0.25 * (((S(A,C) + W(A,p)) + S(B,C)) + W(B,p)) - 0.5 * (S(A,B) + W(C,p))
+ *   L = the sum of these lengths over v = 0 .. 2n-3, v != t0, ascending and sequential, on the host from the device's lengths.
+ *   Nothing is clamped: balanced lengths can be negative and are written as they are.
+ * Candidates.  An internal v with p != t0:  s0 = S(A,B) + W(C,p), s1 = S(A,C) + W(B,p), s2 = W(A,p) + S(B,C),
+ *   g1 = 0.25 * (s0 - s1) (move 1 exchanges B and C), g2 = 0.25 * (s0 - s2) (move 2 exchanges A and C).  The candidate move is
+ *   1 if g1 >= g2, else 2, g its gain; v is a candidate iff g > 0 (a NaN gain is never one; every comparison as written).
+ * Selection.  Candidate v is selected iff no other candidate f has {f, parent(f)} and {v, p} in common and g_f > g_v, or
+ *   g_f == g_v and f < v.
+ * Round.  All selected moves are applied (they touch disjoint node sets; node ids never change, only parents and children),
+ *   the averages are rebuilt, the lengths and L' computed.  L' < L: the round is accepted.  Otherwise it is discarded and, from
+ *   the same tree, only the candidate with the greatest (g, then smaller v) is applied -- a fallback, counted whether or not it
+ *   is accepted -- and accepted if L' < L; if not, the search ends on the tree it had.  The search also ends when a round has no
+ *   candidate, or after max_rounds accepted rounds.  max_rounds = 0: the balanced lengths of the input tree. */
+/* On the device (bme.hip).  Reads the context's FRESH matrix -- after dpr_dist_matrix, before any NJ iteration, in whatever
+ * layout the context's NJ plan gave it -- else DPR_ERR_STATE.  n < 3, n other than the matrix's, a bad log, several ranks,
+ * virtual ranks or virtual shards: DPR_ERR_ARG.  One square fp64 table over the 2n-2 nodes holds S and W (12.8 GB at 20 000
+ * tips); one that does not fit the device's free memory is DPR_ERR_ARG with the bytes needed in the message.  The context
+ * keeps the table: a later call over no more tips allocates nothing; nothing is allocated after the first evaluation of a call.
+ * Non-finite distances are computed with like any other.
+ * kids: 2(n-2) entries, the children of node n+k hung from t0; *top = c; len: 2n-2 entries, the edge above every node (len[c]
+ * is the whole edge t0 - c, len[t0] = 0); L_rounds (may be NULL): max_rounds+1 entries, L of the input tree and after every
+ * accepted round; stats4: accepted rounds, moves applied in them, fallbacks, candidates of the input tree. */
+int dpr_bme_nni(dpr_ctx *ctx, int64_t n, const int32_t *merge_x, const int32_t *merge_y, int max_rounds, int32_t *kids, int32_t *top,
+                double *len, double *L_rounds, int64_t *stats4);
+/* host only, no GPU: the whole loop restated over a table in host memory, rows in rank order -- the reference of the GPU tests.
+ * lower_rows: the strict lower triangle row by row, as dpr_set_matrix_lower takes it. */
+int dpr_bme_nni_host(const double *lower_rows, int64_t n, const int32_t *merge_x, const int32_t *merge_y, int max_rounds, int32_t *kids,
+                     int32_t *top, double *len, double *L_rounds, int64_t *stats4);
+/* host only, no GPU (test hook): one evaluation of the tree given as dpr_bme_nni writes it (kids, top): per node (2n-2 entries
+ * each) the length of the edge above it, the gain g of its candidate move and that move (1, 2; 0: no candidate, gain is then
+ * whatever g came to, 0 for tips and c), and L.  A table that is no binary tree over nodes 0 .. 2n-3 is DPR_ERR_ARG. */
+int dpr_bme_eval_host(const double *lower_rows, int64_t n, const int32_t *kids, int32_t top, double *len, double *gain, int32_t *move,
+                      double *L);
+/* of the last dpr_bme_nni, summed over its evaluations (HIP events): building the table / lengths, gains and their copy back */
+int dpr_get_bme_timing(dpr_ctx *ctx, double *table_ms, double *select_ms);
+/* out4: bytes of the table the context keeps, device allocations dpr_bme_nni has made for this context so far, and of its last
+ * call the kernel launches and the evaluations (table builds) */
+int dpr_get_bme_stats(dpr_ctx *ctx, int64_t *out4);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
