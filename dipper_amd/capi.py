@@ -160,6 +160,12 @@ def load_library():
     L.dpr_bme_eval_host.argtypes = [c_f64p, C.c_int64, c_i32p, C.c_int32, c_f64p, c_f64p, c_i32p, c_f64p]
     L.dpr_get_bme_timing.argtypes = [C.c_void_p, c_f64p, c_f64p]
     L.dpr_get_bme_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_bme_spr.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p] + _bme_out
+    L.dpr_bme_spr_host.argtypes = [c_f64p, C.c_int64, c_i32p, c_i32p] + _bme_out
+    L.dpr_bme_spr_eval_host.argtypes = [c_f64p, C.c_int64, c_i32p, C.c_int32, c_f64p, c_i32p, c_i32p, c_f64p]
+    L.dpr_bme_spr_gain_host.argtypes = [c_f64p, C.c_int64, c_i32p, C.c_int32, C.c_int64, C.c_int32, c_f64p, c_i32p]
+    L.dpr_get_bme_spr_timing.argtypes = [C.c_void_p, c_f64p]
+    L.dpr_get_bme_spr_stats.argtypes = [C.c_void_p, c_i64p]
     L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
     L.dpr_transfer_taxa.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
@@ -362,19 +368,20 @@ def transfer_taxa_host(n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi
     return phi_sum, moved, pairs
 
 
-def _bme_args(n, merge_x, merge_y, max_rounds):
+def _bme_args(n, merge_x, merge_y, max_rounds, nstats=4):
     mx, my = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)[: max(n - 2, 0)]) for a in (merge_x, merge_y))
     assert len(mx) == len(my) == n - 2
     out = dict(kids=np.zeros(2 * max(n - 2, 1), dtype=np.int32), top=np.zeros(1, dtype=np.int32), len=np.zeros(2 * n - 2, dtype=np.float64),
-               L_rounds=np.zeros(max_rounds + 1, dtype=np.float64), stats=np.zeros(4, dtype=np.int64))
+               L_rounds=np.zeros(max_rounds + 1, dtype=np.float64), stats=np.zeros(nstats, dtype=np.int64))
     ptrs = (_p(mx, c_i32p), _p(my, c_i32p), max_rounds, _p(out["kids"], c_i32p), _p(out["top"], c_i32p), _p(out["len"], c_f64p),
             _p(out["L_rounds"], c_f64p), _p(out["stats"], c_i64p))
     return (mx, my), out, ptrs
 
 
 def _bme_result(n, out):
-    rounds, moves, fallbacks, cands0 = (int(v) for v in out["stats"])
-    return dict(kids=out["kids"][: 2 * (n - 2)].reshape(n - 2, 2), top=int(out["top"][0]), len=out["len"], L_rounds=out["L_rounds"][: rounds + 1],
+    rounds, moves, fallbacks, cands0 = (int(v) for v in out["stats"][:4])
+    more = dict(long_moves=int(out["stats"][4]), max_k=int(out["stats"][5])) if len(out["stats"]) == 6 else {}
+    return dict(**more, kids=out["kids"][: 2 * (n - 2)].reshape(n - 2, 2), top=int(out["top"][0]), len=out["len"], L_rounds=out["L_rounds"][: rounds + 1],
                 rounds=rounds, moves=moves, fallbacks=fallbacks, candidates0=cands0)
 
 
@@ -404,6 +411,48 @@ def bme_eval_host(D, kids, top):
     L = C.c_double(0.0)
     _chk(lib, lib.dpr_bme_eval_host(_p(rows, c_f64p), n, _p(kids, c_i32p), int(top), _p(ln, c_f64p), _p(gain, c_f64p), _p(move, c_i32p), C.byref(L)))
     return dict(len=ln, gain=gain, move=move, L=L.value)
+
+
+def _lower_rows(D):
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    return n, (np.ascontiguousarray(np.concatenate([D[i, :i] for i in range(n)])) if n > 1 else np.zeros(1))
+
+
+def bme_spr_host(D, merge_x, merge_y, max_rounds):
+    """Balanced minimum evolution SPR search restated on the host (no GPU): bme_nni_host's arguments and dict, with long_moves
+    (applied moves that carried a subtree past k >= 2 edges) and max_k (the largest k applied) added"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    keep, out, ptrs = _bme_args(n, merge_x, merge_y, max_rounds, 6)
+    _chk(lib, lib.dpr_bme_spr_host(_p(rows, c_f64p), n, *ptrs))
+    return _bme_result(n, out)
+
+
+def bme_spr_eval_host(D, kids, top):
+    """one SPR scan of the tree (kids, top) (host only): dict(gain, w, k, L); per directed subtree d -- d = v: the clade of v,
+    d = (2n-2) + v: outside the clade of v -- its best target's gain, lower node w and path length k (k = 0: none)"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    kids = np.ascontiguousarray(np.asarray(kids, dtype=np.int32).reshape(-1))
+    assert len(kids) == 2 * (n - 2)
+    m2 = 2 * (2 * n - 2)
+    gain, w, k = np.zeros(m2), np.zeros(m2, dtype=np.int32), np.zeros(m2, dtype=np.int32)
+    L = C.c_double(0.0)
+    _chk(lib, lib.dpr_bme_spr_eval_host(_p(rows, c_f64p), n, _p(kids, c_i32p), int(top), _p(gain, c_f64p), _p(w, c_i32p), _p(k, c_i32p), C.byref(L)))
+    return dict(gain=gain, w=w, k=k, L=L.value)
+
+
+def bme_spr_gain_host(D, kids, top, d, w):
+    """(gain, k) of the one SPR move that carries the directed subtree d onto the edge above w (host only); DipperError -1 if w
+    is no target of d"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    kids = np.ascontiguousarray(np.asarray(kids, dtype=np.int32).reshape(-1))
+    assert len(kids) == 2 * (n - 2)
+    g, k = C.c_double(0.0), C.c_int32(0)
+    _chk(lib, lib.dpr_bme_spr_gain_host(_p(rows, c_f64p), n, _p(kids, c_i32p), int(top), int(d), int(w), C.byref(g), C.byref(k)))
+    return g.value, k.value
 
 
 NJ_VARIANT_NJ, NJ_VARIANT_BIONJ = 0, 1
@@ -883,6 +932,25 @@ class Dipper:
         keep, out, ptrs = _bme_args(n, merge_x, merge_y, max_rounds)
         _chk(self.L, self.L.dpr_bme_nni(self.h, n, *ptrs))
         return _bme_result(n, out)
+
+    def bme_spr(self, merge_x, merge_y, max_rounds):
+        """bme_spr_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run)"""
+        n = len(np.asarray(merge_x)) + 2
+        keep, out, ptrs = _bme_args(n, merge_x, merge_y, max_rounds, 6)
+        _chk(self.L, self.L.dpr_bme_spr(self.h, n, *ptrs))
+        return _bme_result(n, out)
+
+    def bme_spr_timing(self):
+        """scan ms of the last bme_spr, summed over its evaluations (bme_timing gives the table and lengths of the same call)"""
+        a = C.c_double()
+        _chk(self.L, self.L.dpr_get_bme_spr_timing(self.h, C.byref(a)))
+        return a.value
+
+    def bme_spr_stats(self):
+        """dict(stack_bytes, allocations so far beyond the table's, scan launches of the last bme_spr, workers)"""
+        out = np.zeros(4, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_bme_spr_stats(self.h, _p(out, c_i64p)))
+        return dict(stack_bytes=int(out[0]), allocations=int(out[1]), launches=int(out[2]), workers=int(out[3]))
 
     def bme_timing(self):
         """(table ms, lengths + gains ms) of the last bme_nni, summed over its evaluations"""

@@ -1,13 +1,15 @@
-// Balanced minimum evolution (Desper & Gascuel 2002): the parts of the NNI search that are the same on the host and on the device.
+// Balanced minimum evolution (Desper & Gascuel 2002): the parts of the NNI and SPR searches that are the same on the host and on the device.
 // Plain C++ (no HIP call, no library state), so that a stand-alone program can include it: the tree and its bookkeeping, the
 // selection of a round's moves, the search loop, the per-node arithmetic (marked for both sides when hipcc compiles it) and the
 // host engine behind dpr_bme_nni_host.  The contract is in include/dipper_hip.h above dpr_bme_nni; bme.hip holds the kernels.
 //
 // One square table T over the M = 2n - 2 nodes, row stride ld: T[u][v] = S(u, v) where neither node is an ancestor of the
-// other (both orientations are kept), T[u][v] = W(u, v) where v is a proper ancestor of u.  T[v][u] of such a pair is unused.
+// other (both orientations are kept), T[u][v] = W(u, v) where v is a proper ancestor of u.  T[v][u] of such a pair is unused by
+// the NNI search; the SPR scan mirrors W into it (spr_mirror_w below).
 // The host engine indexes T by node id; the device engine by the node's place in rank order (View::pos), which makes the rows
 // of one height neighbours.  Which element holds a value has no part in the arithmetic.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -365,6 +367,431 @@ inline int eval_host(const double* lower_rows, int64_t n, const int32_t* kids, i
     std::copy(e.len.begin(), e.len.end(), len);
     std::copy(e.gain.begin(), e.gain.end(), gain);
     std::copy(e.move.begin(), e.move.end(), move);
+    *L = e.L;
+    return 0;
+}
+
+// ---- SPR (subtree pruning and regrafting): the contract is in include/dipper_hip.h above dpr_bme_spr ----------------------------
+// The scan reads T through the unordered pair of the two subtrees' nodes: the subtree seen from p towards a neighbour is named by
+// the lower node of that edge (the clade of a child, or everything outside the clade of p; outside the clade of `top` is the tip
+// t0).  Two disjoint subtrees' nodes are either unrelated (S) or one is an ancestor of the other (W), so once W is mirrored into
+// the elements T[ancestor][node], which nothing else reads, T[a][b] is the average of the pair in either orientation.
+DPR_BME_HD inline void spr_mirror_w(double* T, int64_t ld, int64_t M, const View& t, int32_t u)
+{
+    if (u == t.t0 || u == t.top) return;
+    const int64_t cu = t.at(u);
+    int32_t v = t.par[u];
+    for (int64_t step = 0; step < M && v != t.t0; ++step) {
+        const int64_t cv = t.at(v);
+        T[cv * ld + cu] = T[cu * ld + cv];
+        v = t.par[v];
+    }
+}
+
+// one node as the scan reads it: children (-1: a tip), parent, nodes in its clade -- in the index space of T
+struct SprRec { int32_t k0, k1, par, size; };
+struct SprTree {
+    const double* T;
+    int64_t ld;
+    const SprRec* rec;
+    const int32_t* ids;      // node id of every index; null: itself
+    const double* trio;      // per node p three averages between the subtrees at p: (k0, k1), (k0, outside p), (k1, outside p); null: read from T
+    int32_t n, M, t0, top;   // tips are the indices below n in either space
+    DPR_BME_HD int32_t id(int32_t v) const { return ids ? ids[v] : v; }
+    DPR_BME_HD int32_t lower(int32_t c) const { return id(c == t0 ? top : c); }      // the edge at t0 is the one above `top`
+};
+
+// the best target of one pruned subtree so far (k = 0: none); want >= 0: the gain of that target alone, whatever it is
+struct SprBest {
+    double g = 0.0;
+    int32_t w = -1, k = 0, want = -1;
+    DPR_BME_HD void merge(double g2, int32_t w2, int32_t k2)      // w2: a node id
+    {
+        if (k == 0 || g2 > g || (g2 == g && w2 < w)) { g = g2; w = w2; k = k2; }
+    }
+    DPR_BME_HD void take(const SprTree& t, double g2, int32_t wplace, int32_t k2)
+    {
+        if (want >= 0) {
+            if (t.lower(wplace) == want) { g = g2; w = want; k = k2; }
+            return;
+        }
+        if (!(g2 == g2) || (k != 0 && !(g2 >= g))) return;
+        merge(g2, t.lower(wplace), k2);
+    }
+};
+
+// where one traversal stands: the rows of X and A, d(X, A), and the path node to visit next with the sums of the path before it
+struct SprState {
+    int64_t xr, ar;
+    double dXA, U, V, h;
+    int32_t p, from, k;
+};
+
+// the two neighbours of a node other than x, in the order (k0, k1, par)
+DPR_BME_HD inline void spr_others(const SprRec& r, int32_t x, int32_t* o0, int32_t* o1)
+{
+    if (x == r.k0) { *o0 = r.k1; *o1 = r.par; }
+    else if (x == r.k1) { *o0 = r.k0; *o1 = r.par; }
+    else { *o0 = r.k0; *o1 = r.k1; }
+}
+
+DPR_BME_HD inline double spr_gain(double h, double dXA, double xB, double Uk, double Vk, double yB, double cB, double aB)
+{
+    return (((0.5 - h) * (dXA - xB) + (Uk - Vk)) + 0.25 * (yB + cB)) - (0.5 * h) * (aB + xB);
+}
+
+// Directed subtree dp (index v: the clade of v; M + v: outside the clade of v), direction 0 / 1 = which of q's two other
+// neighbours the path leaves through.  false: not prunable, or nothing to visit that way.
+DPR_BME_HD inline bool spr_begin(const SprTree& t, int32_t dp, int dir, SprState& s)
+{
+    const bool outside = dp >= t.M;
+    const int32_t v = outside ? dp - t.M : dp;
+    const SprRec rv = t.rec[v];
+    int32_t x0, q, xnode;
+    if (!outside) {
+        if (v == t.t0 || v == t.top) return false;
+        x0 = v; q = rv.par; xnode = v;
+    } else {
+        if (rv.k0 < 0) return false;
+        q = v; x0 = rv.par; xnode = v == t.top ? t.t0 : v;
+    }
+    const SprRec rq = t.rec[q];
+    int32_t o0, o1;
+    spr_others(rq, x0, &o0, &o1);
+    const int32_t p1 = dir ? o1 : o0, a0 = dir ? o0 : o1;
+    if (p1 < t.n) return false;
+    const int32_t anode = (a0 != rq.par || q == t.top) ? a0 : q;
+    s.xr = (int64_t)xnode * t.ld; s.ar = (int64_t)anode * t.ld;
+    s.dXA = t.T[s.xr + anode];
+    s.U = 0.0; s.V = 0.0; s.h = 0.5;
+    s.p = p1; s.from = q; s.k = 0;
+    return true;
+}
+
+// Visit path node s.p: its two targets, then on to the next path node -- the smaller of two internal continuations first, the
+// larger one stacked, which keeps the stack below log2 M entries.  false: the traversal is over.
+template <class Stack>
+DPR_BME_HD inline bool spr_step(const SprTree& t, SprState& s, SprBest& b, Stack& st)
+{
+    const int32_t p = s.p;
+    const SprRec r = t.rec[p];
+    int32_t n1, n2;
+    spr_others(r, s.from, &n1, &n2);
+    const bool attop = p == t.top;
+    const int32_t c1 = (n1 != r.par || attop) ? n1 : p, c2 = (n2 != r.par || attop) ? n2 : p, cc = (s.from != r.par || attop) ? s.from : p;
+    const int32_t k = s.k + 1;
+    const double h = 0.5 * s.h;
+    const double* T = t.T;
+    const double x1 = T[s.xr + c1], x2 = T[s.xr + c2], a1 = T[s.ar + c1], a2 = T[s.ar + c2];
+    double y, cb1, cb2;                                      // d(Y_k, B) and d(C_k, B) of the two targets: the same for every X
+    if (t.trio) {
+        const double* q3 = t.trio + 3 * (int64_t)p;
+        const double d01 = q3[0], d0p = q3[1], d1p = q3[2];
+        if (s.from == r.k0) { y = d1p; cb1 = d01; cb2 = d0p; }
+        else if (s.from == r.k1) { y = d0p; cb1 = d01; cb2 = d1p; }
+        else { y = d01; cb1 = d0p; cb2 = d1p; }
+    } else {
+        y = T[(int64_t)c1 * t.ld + c2]; cb1 = T[(int64_t)cc * t.ld + c1]; cb2 = T[(int64_t)cc * t.ld + c2];
+    }
+    const double U1 = s.U + h * (x2 - a2), V1 = 0.5 * s.V + 0.25 * x2;      // on towards n1: Y_k is beyond n2
+    const double U2 = s.U + h * (x1 - a1), V2 = 0.5 * s.V + 0.25 * x1;      // on towards n2
+    b.take(t, spr_gain(h, s.dXA, x1, U1, V1, y, cb1, a1), c1, k);
+    b.take(t, spr_gain(h, s.dXA, x2, U2, V2, y, cb2, a2), c2, k);
+    const bool i1 = n1 >= t.n, i2 = n2 >= t.n;
+    if (i1 && i2) {
+        const int32_t s1 = c1 == n1 ? t.rec[n1].size : t.M - r.size, s2 = c2 == n2 ? t.rec[n2].size : t.M - r.size;
+        const bool first1 = s1 <= s2;
+        st.push(first1 ? n2 : n1, p, k, first1 ? U2 : U1, first1 ? V2 : V1, h);
+        s.p = first1 ? n1 : n2; s.U = first1 ? U1 : U2; s.V = first1 ? V1 : V2;
+    } else if (i1 || i2) {
+        s.p = i1 ? n1 : n2; s.U = i1 ? U1 : U2; s.V = i1 ? V1 : V2;
+    } else {
+        return st.pop(s);
+    }
+    s.from = p; s.k = k; s.h = h;
+    return true;
+}
+
+// ---- host only from here ------------------------------------------------------------------------------------------------------
+constexpr int kSprStack = 32;      // log2 M < 25 entries are ever held (n < 2^24)
+struct SprHostStack {
+    struct Entry { double U, V, h; int32_t p, from, k; } e[kSprStack];
+    int sp = 0;
+    void push(int32_t p, int32_t from, int32_t k, double U, double V, double h)
+    {
+        if (sp < kSprStack) e[sp++] = Entry{ U, V, h, p, from, k };
+    }
+    bool pop(SprState& s)
+    {
+        if (sp == 0) return false;
+        const Entry& x = e[--sp];
+        s.U = x.U; s.V = x.V; s.h = x.h; s.p = x.p; s.from = x.from; s.k = x.k;
+        return true;
+    }
+};
+
+// per directed subtree d (2M entries): gain, target w and path length k of its best target (k = 0: none, gain 0, w -1)
+struct SprEval {
+    std::vector<double> gain;
+    std::vector<int32_t> w, k;
+    void size(int64_t M) { gain.resize((size_t)(2 * M)); w.resize((size_t)(2 * M)); k.resize((size_t)(2 * M)); }
+};
+
+// the scan's view of a derived tree: 4 M ints of records at out, M ints of node ids at out + ids_off.  places: in rank-order
+// places (the device table), else in node ids (the host table)
+inline void spr_records(const Tree& t, bool places, int32_t* out, int64_t ids_off)
+{
+    for (int64_t v = 0; v < t.M; ++v) {
+        auto at = [&](int32_t u) { return u < 0 || !places ? u : t.pos[(size_t)u]; };
+        const int64_t p = at((int32_t)v);
+        out[4 * p] = at(t.kid0[(size_t)v]); out[4 * p + 1] = at(t.kid1[(size_t)v]); out[4 * p + 2] = at(t.par[(size_t)v]);
+        out[4 * p + 3] = t.tout[(size_t)v] - t.tin[(size_t)v];
+        out[ids_off + p] = (int32_t)v;
+    }
+}
+
+inline void spr_scan_one(const SprTree& st, int32_t d, SprBest& b)
+{
+    for (int dir = 0; dir < 2; ++dir) {
+        SprState s;
+        SprHostStack stack;
+        bool live = spr_begin(st, d, dir, s);
+        for (int64_t step = 0; live && step < st.M; ++step) live = spr_step(st, s, b, stack);
+    }
+}
+
+// the nodes of the move (d, w): x0, a0, q, p_1 .. p_k, b0 appended to out; returns k
+inline int32_t spr_path(const Tree& t, int32_t d, int32_t w, std::vector<int32_t>& out)
+{
+    const View vw = t.view();
+    const bool outside = d >= t.M;
+    const int32_t v = outside ? d - (int32_t)t.M : d;
+    const int32_t x0 = outside ? t.par[(size_t)v] : v, q = outside ? v : t.par[(size_t)v];
+    const size_t base = out.size();
+    out.push_back(x0); out.push_back(-1); out.push_back(q);
+    int32_t b0;
+    if (in_clade(vw, w, q)) {                                // w is above q: up to w, the target is the edge above it
+        for (int32_t a = q; a != w;) { a = t.par[(size_t)a]; out.push_back(a); }
+        b0 = t.par[(size_t)w];
+    } else {                                                 // up to the last common ancestor, then down to parent(w)
+        int32_t a = q;
+        while (!in_clade(vw, a, w)) { a = t.par[(size_t)a]; out.push_back(a); }
+        const size_t mid = out.size();
+        for (int32_t c = t.par[(size_t)w]; c != a; c = t.par[(size_t)c]) out.push_back(c);
+        std::reverse(out.begin() + (std::ptrdiff_t)mid, out.end());
+        b0 = w;
+    }
+    out.push_back(b0);
+    const int32_t p1 = out[base + 3];
+    const int32_t nbq[3] = { t.kid0[(size_t)q], t.kid1[(size_t)q], t.par[(size_t)q] };
+    for (int32_t c : nbq)
+        if (c != x0 && c != p1) out[base + 1] = c;
+    return (int32_t)(out.size() - base) - 4;
+}
+
+// the moves of a round: node sets one after another in `nodes`, move i at [off[i], off[i + 1]), its subtree d[i]
+struct SprMoves {
+    std::vector<int32_t> nodes, d;
+    std::vector<size_t> off;
+    std::vector<int32_t> order;
+    std::vector<uint8_t> mark;
+    size_t count() const { return d.size(); }
+    int32_t k(size_t i) const { return (int32_t)(off[i + 1] - off[i]) - 4; }
+};
+
+// candidates by (gain descending, d ascending), each selected iff its nodes are free; returns the number of candidates
+inline int64_t spr_select(const Tree& t, const SprEval& e, SprMoves& m)
+{
+    m.nodes.clear(); m.d.clear(); m.off.assign(1, 0); m.order.clear();
+    m.mark.assign((size_t)t.M, 0);
+    for (int64_t d = 0; d < 2 * t.M; ++d)
+        if (e.k[(size_t)d] != 0 && e.gain[(size_t)d] > 0) m.order.push_back((int32_t)d);
+    std::sort(m.order.begin(), m.order.end(), [&](int32_t a, int32_t b) {
+        return e.gain[(size_t)a] > e.gain[(size_t)b] || (e.gain[(size_t)a] == e.gain[(size_t)b] && a < b);
+    });
+    for (int32_t d : m.order) {
+        const size_t base = m.nodes.size();
+        spr_path(t, d, e.w[(size_t)d], m.nodes);
+        bool is_free = true;
+        for (size_t i = base; i < m.nodes.size(); ++i) is_free = is_free && !m.mark[(size_t)m.nodes[i]];
+        if (!is_free) { m.nodes.resize(base); continue; }
+        for (size_t i = base; i < m.nodes.size(); ++i) m.mark[(size_t)m.nodes[i]] = 1;
+        m.d.push_back(d);
+        m.off.push_back(m.nodes.size());
+    }
+    return (int64_t)m.order.size();
+}
+
+// moves [first, last) applied to the unrooted tree (q leaves between a0 and p_1 and enters between p_k and b0), re-hung from t0
+inline bool spr_apply(Tree& t, const SprMoves& m, size_t first, size_t last, std::vector<int32_t>& nb)
+{
+    const int64_t M = t.M;
+    nb.assign((size_t)(3 * M), -1);
+    for (int64_t v = 0; v < M; ++v) {
+        nb[(size_t)(3 * v)] = t.par[(size_t)v];
+        nb[(size_t)(3 * v + 1)] = t.kid0[(size_t)v];
+        nb[(size_t)(3 * v + 2)] = t.kid1[(size_t)v];
+    }
+    auto rep = [&](int32_t node, int32_t old, int32_t nw) {
+        for (int e = 0; e < 3; ++e)
+            if (nb[(size_t)(3 * node + e)] == old) { nb[(size_t)(3 * node + e)] = nw; return; }
+    };
+    for (size_t i = first; i < last; ++i) {
+        const int32_t* s = m.nodes.data() + m.off[i];
+        const size_t cnt = m.off[i + 1] - m.off[i];
+        const int32_t a0 = s[1], q = s[2], p1 = s[3], pk = s[cnt - 2], b0 = s[cnt - 1];
+        rep(a0, q, p1); rep(p1, q, a0);
+        rep(pk, b0, q); rep(b0, pk, q);
+        rep(q, a0, b0);
+        if (p1 != pk) rep(q, p1, pk);
+    }
+    t.kid0.assign((size_t)M, -1); t.kid1.assign((size_t)M, -1); t.par.assign((size_t)M, -1);
+    t.top = nb[(size_t)(3 * t.t0)];
+    if (t.top < t.n) return false;
+    t.par[(size_t)t.t0] = t.top; t.par[(size_t)t.top] = t.t0;
+    t.stack.assign(1, t.top);
+    int64_t seen = 0;
+    while (!t.stack.empty()) {
+        const int32_t v = t.stack.back();
+        t.stack.pop_back();
+        if (++seen > M) return false;
+        if (v < t.n) continue;
+        int32_t k[2] = { -1, -1 }, c = 0;
+        for (int e = 0; e < 3; ++e) {
+            const int32_t u = nb[(size_t)(3 * v + e)];
+            if (u == t.par[(size_t)v]) continue;
+            if (u < 0 || c == 2) return false;
+            k[c++] = u;
+        }
+        if (c != 2) return false;
+        t.kid0[(size_t)v] = std::min(k[0], k[1]); t.kid1[(size_t)v] = std::max(k[0], k[1]);
+        t.par[(size_t)k[0]] = t.par[(size_t)k[1]] = v;
+        t.stack.push_back(k[0]); t.stack.push_back(k[1]);
+    }
+    return seen == M - 1;
+}
+
+// The SPR search.  engine(tree, eval, spr_eval) evaluates a derived tree (0, or an error code that ends the search).
+template <class Engine>
+inline int spr_search(Tree& t, int max_rounds, Engine&& engine, Eval& cur, double* L_rounds, int64_t* stats6)
+{
+    Eval nxt;
+    SprEval scur, snxt;
+    cur.size(t.M); nxt.size(t.M); scur.size(t.M); snxt.size(t.M);
+    SprMoves mv;
+    std::vector<int32_t> k0, k1, pr, nb;
+    derive(t);
+    if (int rc = engine(t, cur, scur)) return rc;
+    if (L_rounds) L_rounds[0] = cur.L;
+    for (int i = 0; i < 6; ++i) stats6[i] = 0;
+    for (int rounds = 0;;) {
+        const int64_t cands = spr_select(t, scur, mv);
+        if (rounds == 0) stats6[3] = cands;
+        if (cands == 0 || rounds >= max_rounds) break;
+        k0 = t.kid0; k1 = t.kid1; pr = t.par;
+        const int32_t top0 = t.top;
+        auto restore = [&]() { t.kid0 = k0; t.kid1 = k1; t.par = pr; t.top = top0; };
+        if (!spr_apply(t, mv, 0, mv.count(), nb)) return -1;
+        derive(t);
+        if (int rc = engine(t, nxt, snxt)) return rc;
+        size_t applied = mv.count();
+        if (!(nxt.L < cur.L)) {
+            ++stats6[2];
+            restore();
+            if (!spr_apply(t, mv, 0, 1, nb)) return -1;
+            derive(t);
+            if (int rc = engine(t, nxt, snxt)) return rc;
+            applied = 1;
+            if (!(nxt.L < cur.L)) {
+                restore();
+                derive(t);
+                break;
+            }
+        }
+        std::swap(cur, nxt);
+        std::swap(scur, snxt);
+        stats6[1] += (int64_t)applied;
+        for (size_t i = 0; i < applied; ++i) {
+            stats6[4] += mv.k(i) >= 2;
+            stats6[5] = std::max<int64_t>(stats6[5], mv.k(i));
+        }
+        stats6[0] = ++rounds;
+        if (L_rounds) L_rounds[rounds] = cur.L;
+    }
+    return 0;
+}
+
+// the host engine with the scan behind it: the table in node ids
+struct SprHostEngine {
+    HostEngine base;
+    std::vector<int32_t> tab;
+    SprTree prepare(const Tree& t)
+    {
+        const View w = t.view();
+        for (int32_t u = 0; u < t.M; ++u) spr_mirror_w(base.T.data(), base.ld, t.M, w, u);
+        tab.resize((size_t)(5 * t.M));
+        spr_records(t, false, tab.data(), 4 * t.M);
+        return SprTree{ base.T.data(), base.ld, reinterpret_cast<const SprRec*>(tab.data()), nullptr, nullptr, (int32_t)t.n, (int32_t)t.M, t.t0, t.top };
+    }
+    int operator()(const Tree& t, Eval& e, SprEval& se)
+    {
+        base(t, e);
+        const SprTree st = prepare(t);
+        for (int64_t d = 0; d < 2 * t.M; ++d) {
+            SprBest b;
+            spr_scan_one(st, (int32_t)d, b);
+            se.gain[(size_t)d] = b.g; se.w[(size_t)d] = b.w; se.k[(size_t)d] = b.k;
+        }
+        return 0;
+    }
+};
+
+// dpr_bme_spr_host without the library around it: 0, or -1 (bad argument / not a merge log)
+inline int spr_host(const double* lower_rows, int64_t n, const int32_t* mx, const int32_t* my, int max_rounds, int32_t* kids, int32_t* top,
+                    double* len, double* L_rounds, int64_t* stats6)
+{
+    if (!lower_rows || n < 3 || n >= ((int64_t)1 << 24) || !mx || !my || max_rounds < 0 || !kids || !top || !len || !stats6) return -1;
+    Tree t;
+    if (!from_merges(n, mx, my, t)) return -1;
+    SprHostEngine eng;
+    eng.base.fill(n, lower_rows);
+    Eval cur;
+    if (int rc = spr_search(t, max_rounds, eng, cur, L_rounds, stats6)) return rc;
+    write_outputs(t, cur, kids, top, len);
+    return 0;
+}
+
+// one scan of a given tree on the host (test hooks dpr_bme_spr_eval_host; d >= 0: dpr_bme_spr_gain_host, the gain and k of the
+// target w of d alone, -2 if w is no target of d): 0, or -1
+inline int spr_eval_host(const double* lower_rows, int64_t n, const int32_t* kids, int32_t top, int64_t d, int32_t w, double* gain, int32_t* bw,
+                         int32_t* bk, double* L)
+{
+    if (!lower_rows || n < 3 || n >= ((int64_t)1 << 24) || !kids || !gain || !bk) return -1;
+    Tree t;
+    if (!from_kids(n, kids, top, t)) return -1;
+    derive(t);
+    SprHostEngine eng;
+    eng.base.fill(n, lower_rows);
+    Eval e;
+    e.size(t.M);
+    if (d >= 0) {
+        if (d >= 2 * t.M || w < 0 || w >= t.M) return -2;
+        eng.base(t, e);
+        const SprTree st = eng.prepare(t);
+        SprBest b;
+        b.want = w;
+        spr_scan_one(st, (int32_t)d, b);
+        if (b.k == 0) return -2;
+        *gain = b.g; *bk = b.k;
+        return 0;
+    }
+    if (!bw || !L) return -1;
+    SprEval se;
+    se.size(t.M);
+    eng(t, e, se);
+    std::copy(se.gain.begin(), se.gain.end(), gain);
+    std::copy(se.w.begin(), se.w.end(), bw);
+    std::copy(se.k.begin(), se.k.end(), bk);
     *L = e.L;
     return 0;
 }

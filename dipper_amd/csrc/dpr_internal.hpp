@@ -461,6 +461,16 @@ struct BmeBuffers {
     int64_t allocations = 0;             // device allocations made for this context so far
     int64_t launches = 0, evaluations = 0;       // kernels / table builds of the last call
     double table_ms = 0, select_ms = 0;  // of the last call: table (fill, S, W) / lengths + gains and their copy back (HIP events)
+    // dpr_bme_spr only (none of it is allocated before its first call)
+    DevBuf<int32_t> spr_tab;             // [5][spr_ldi]: per place of T the record kid0, kid1, par, clade size (places), then the node id of every place
+    DevBuf<double> spr_gain;             // [9][spr_ldi]: best gain per (directed subtree, side) (4), per directed subtree (2); three averages per place (3)
+    DevBuf<int32_t> spr_wk;              // [12][spr_ldi]: target w and path length k per (subtree, side) (4 + 4), per subtree (2 + 2)
+    DevBuf<double> spr_dstack;           // traversal stacks of the scan, one column per resident thread: U, V, h ...
+    DevBuf<int32_t> spr_istack;          // ... and node, node before it, k
+    int64_t spr_ldi = 0;                 // stride the three arrays above were sized for
+    int64_t spr_allocations = 0;         // device allocations dpr_bme_spr has made for this context beyond the table's
+    int64_t spr_launches = 0;            // scan kernels of the last dpr_bme_spr
+    double spr_scan_ms = 0;              // of the last dpr_bme_spr: mirror, scan, best and their copy back (HIP events)
 };
 
 // mash.hip

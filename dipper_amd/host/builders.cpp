@@ -212,7 +212,7 @@ void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<st
 }
 
 void NJDeviceArrays::findRefinedTree(DeviceContext& dev, Param& params, MatrixReader* matrixReader, std::vector<std::string>& name,
-                                     std::ostream& output_, int rounds)
+                                     std::ostream& output_, int rounds, bool spr)
 {
     const int N = d_numSequences;
     std::vector<int32_t> mx((size_t)std::max(N - 2, 1)), my((size_t)std::max(N - 2, 1));
@@ -222,15 +222,25 @@ void NJDeviceArrays::findRefinedTree(DeviceContext& dev, Param& params, MatrixRe
     std::vector<int32_t> kids((size_t)(2 * std::max(N - 2, 1)));
     std::vector<double> len((size_t)(2 * N - 2)), L((size_t)rounds + 1, 0.0);
     int32_t top = 0;
-    int64_t stats[4] = { 0, 0, 0, 0 };
-    gpuCheck(dpr_bme_nni(dev.ctx, N, mx.data(), my.data(), rounds, kids.data(), &top, len.data(), L.data(), stats), "dpr_bme_nni");
+    int64_t stats[6] = { 0, 0, 0, 0, 0, 0 };
+    if (spr) gpuCheck(dpr_bme_spr(dev.ctx, N, mx.data(), my.data(), rounds, kids.data(), &top, len.data(), L.data(), stats), "dpr_bme_spr");
+    else gpuCheck(dpr_bme_nni(dev.ctx, N, mx.data(), my.data(), rounds, kids.data(), &top, len.data(), L.data(), stats), "dpr_bme_nni");
     writeNewickFromKids(output_, name, kids, top, len);
-    std::cerr << "BME NNI: L " << L[0] << " -> " << L[(size_t)stats[0]] << ", " << stats[1] << " moves, " << stats[0] << " rounds, " << stats[2]
-              << " fallbacks\n";
+    if (spr)
+        std::cerr << "BME SPR: L " << L[0] << " -> " << L[(size_t)stats[0]] << ", " << stats[1] << " moves (" << stats[4] << " beyond NNI, longest "
+                  << stats[5] << "), " << stats[0] << " rounds, " << stats[2] << " fallbacks\n";
+    else
+        std::cerr << "BME NNI: L " << L[0] << " -> " << L[(size_t)stats[0]] << ", " << stats[1] << " moves, " << stats[0] << " rounds, " << stats[2]
+                  << " fallbacks\n";
     if (cliLog()) {
-        double table_ms = 0, select_ms = 0;
+        double table_ms = 0, select_ms = 0, scan_ms = 0;
         dpr_get_bme_timing(dev.ctx, &table_ms, &select_ms);
-        std::cerr << "  device: BME tables " << table_ms << " ms, lengths and gains " << select_ms << " ms\n";
+        std::cerr << "  device: BME tables " << table_ms << " ms, lengths and gains " << select_ms << " ms";
+        if (spr) {
+            dpr_get_bme_spr_timing(dev.ctx, &scan_ms);
+            std::cerr << ", SPR scans " << scan_ms << " ms";
+        }
+        std::cerr << "\n";
     }
 }
 

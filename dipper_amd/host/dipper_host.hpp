@@ -168,9 +168,10 @@ struct NJDeviceArrays {  // src/mash_placement.cuh:199-212
     void getDismatrix(DeviceContext& dev, int numSequences, Param& params, MatrixReader* matrixReader);
     void findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_);
     // --nni R: the NJ / BIONJ tree as above, the distance matrix built again, at most R rounds of balanced minimum evolution NNI
-    // on it (dpr_bme_nni) and the tree it ends on with its balanced branch lengths; one line on stderr
+    // on it (dpr_bme_nni) and the tree it ends on with its balanced branch lengths; one line on stderr.  spr (--spr R): the SPR
+    // search of dpr_bme_spr in its place
     void findRefinedTree(DeviceContext& dev, Param& params, MatrixReader* matrixReader, std::vector<std::string>& name, std::ostream& output_,
-                         int rounds);
+                         int rounds, bool spr = false);
 };
 
 struct MashDeviceArrays {  // src/mash_placement.cuh:34-50

@@ -95,6 +95,11 @@ static const char* kHelp =
     "                              the NJ topology).  Wherever conventional NJ builds the tree (-m 2, or -m 0\n"
     "                              below 30000; -i d, m or r; --protein; --bionj; every -d); one GPU.  Not\n"
     "                              with -m 1, -m 3, --add, -o d, -o j, --bootstrap or several ranks\n"
+    "  --spr arg                   As --nni, with subtree pruning and regrafting moves: a subtree may be carried\n"
+    "                              past any number of edges in one move (an interchange is the move past one),\n"
+    "                              which leaves optima that hold --nni.  At most arg >= 0 rounds, each applying\n"
+    "                              every improving move that shares no node with a better one.  Valid where\n"
+    "                              --nni is; not together with --nni\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -123,7 +128,7 @@ static const Opt kOpts[] = {
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
-    { "bionj", 0, false }, { "nni", 0, true },
+    { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -309,18 +314,21 @@ int main(int argc, char** argv)
         if (out == "d" || out == "j") usageError("--bionj needs tree output (-o t)");
         bionjOption() = true;      // every context of this command builds BIONJ trees (DeviceContext, the bootstrap's rank-local one)
     }
-    // --nni: what the arguments alone decide, before any input is read or a GPU touched (several ranks: below, once they are parsed)
+    // --nni / --spr: what the arguments alone decide, before any input is read or a GPU touched (several ranks: below, once they are parsed)
     int nni = -1;
-    if (vm.count("nni")) {
-        const std::string nv = vm["nni"], al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
+    const bool spr = vm.count("spr") != 0;
+    const std::string refine = spr ? "--spr" : "--nni";
+    if (spr && vm.count("nni")) usageError("--spr is not supported with --nni (an SPR search contains the NNI moves)");
+    if (vm.count("nni") || spr) {
+        const std::string nv = vm[spr ? "spr" : "nni"], al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
         bool digits = !nv.empty() && nv.size() <= 9;
         for (char ch : nv) digits = digits && std::isdigit((unsigned char)ch);
-        if (!digits) usageError("--nni: the number of rounds must be a whole number >= 0");
+        if (!digits) usageError(refine + ": the number of rounds must be a whole number >= 0");
         nni = std::stoi(nv);
-        if (al == "1" || al == "3") usageError("--nni needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
-        if (vm.count("add")) usageError("--nni is not supported with --add");
-        if (out == "d" || out == "j") usageError("--nni needs tree output (-o t)");
-        if (vm.count("bootstrap")) usageError("--nni is not supported with --bootstrap (replicate trees are not refined)");
+        if (al == "1" || al == "3") usageError(refine + " needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add")) usageError(refine + " is not supported with --add");
+        if (out == "d" || out == "j") usageError(refine + " needs tree output (-o t)");
+        if (vm.count("bootstrap")) usageError(refine + " is not supported with --bootstrap (replicate trees are not refined)");
     }
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
@@ -441,7 +449,7 @@ int main(int argc, char** argv)
     }
     const bool multi = ranks.multi();
     if (nni >= 0 && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
-        usageError("--nni runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
+        usageError(refine + " runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
     if (!multi && ranks.devices.size() == 1) device = ranks.devices[0];      // (`--devices 3` alone: one rank on GPU 3)
 
     const int placement_thr = 30000, dc_thr = 1000000;  // src/tree_generation.cu:247-248
@@ -685,7 +693,7 @@ int main(int argc, char** argv)
             die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (nni >= 0 && pick_mode((long long)numSequences) != 2)
-            die("ERROR: --nni needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+            die("ERROR: " + refine + " needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (protein && pick_mode((long long)numSequences) == 3)
             die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
@@ -768,7 +776,7 @@ int main(int argc, char** argv)
                 bootstrapNeighbourJoiningTree(dev, (int)numSequences, params, boot, packed.ok ? packed.flat.data() : flat.data(),
                                               seqLen, names, *output_);
             } else if (nni >= 0) {
-                njDeviceArrays.findRefinedTree(dev, params, nullptr, names, *output_, nni);
+                njDeviceArrays.findRefinedTree(dev, params, nullptr, names, *output_, nni, spr);
             } else {
                 njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
             }
@@ -800,7 +808,7 @@ int main(int argc, char** argv)
             die("ERROR: --bionj needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (nni >= 0 && mode != 2)
-            die("ERROR: --nni needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+            die("ERROR: " + refine + " needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (mode == 3) { std::cerr << "Divide-and-conquer mode not supported with input matrix\n"; return 1; }
         if (multi) startRanks(ranks, device);
@@ -820,7 +828,7 @@ int main(int argc, char** argv)
                 std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
             NJDeviceArrays njDeviceArrays;
             njDeviceArrays.getDismatrix(dev, numSequences, params, &matrixReader);
-            if (nni >= 0) njDeviceArrays.findRefinedTree(dev, params, &matrixReader, matrixReader.name, *output_, nni);
+            if (nni >= 0) njDeviceArrays.findRefinedTree(dev, params, &matrixReader, matrixReader.name, *output_, nni, spr);
             else njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_);
         }
         printRankSummary(dev.ctx);

@@ -632,6 +632,54 @@ int dpr_get_bme_timing(dpr_ctx *ctx, double *table_ms, double *select_ms);
  * call the kernel launches and the evaluations (table builds) */
 int dpr_get_bme_stats(dpr_ctx *ctx, int64_t *out4);
 
+/* ---- balanced minimum evolution: SPR search (subtree pruning and regrafting, the BME search of FastME; an NNI is the case
+ * k = 1).  Tree, averages, lengths, L and the acceptance rule are those of the NNI contract above; fp64, exactly this order of
+ * operations, no contraction; the device and dpr_bme_spr_host produce the same bits.
+ * Pruned subtrees.  X is one side of an edge {x0, q}, q internal: the clade of v (x0 = v, q = parent(v), v not t0, not c), numbered
+ *   d = v; or everything outside the clade of an internal v (q = v, x0 = parent(v); for v = c this is the tip t0), numbered
+ *   d = (2n-2) + v.  3 (n-2) directed subtrees.
+ * Path.  a0 and p_1 are q's other two neighbours (either way round); q, p_1 .. p_k, k >= 1, all p_i internal, leads away from X;
+ *   b0 is a neighbour of p_k other than p_(k-1) (q for k = 1), and the last neighbour of p_k is the root of Y_k.  A, B, Y_i are
+ *   the subtrees beyond a0, b0 and off p_i; C_k is the subtree at p_k towards p_(k-1).  The move takes q out (a0 joins p_1) and
+ *   puts it on the edge {p_k, b0}; the target is named by w, the lower node of that edge (w != t0).  Edges at q and inside X are
+ *   no targets.
+ * d(P,Q) of two disjoint subtrees is S(u,v) of their clade nodes, or W(u,v) where Q is the outside of the clade of v (outside
+ *   the clade of c: the tip t0, S(u,t0)).
+ * Gain.  h_0 = 0.5, h_k = 0.5 * h_(k-1) (exact powers of two, 0 from k = 1074 on); U_0 = V_0 = 0;
+ *   U_k = U_(k-1) + h_k * (d(X,Y_k) - d(A,Y_k));   V_k = 0.5 * V_(k-1) + 0.25 * d(X,Y_k);
+ *   g_k = (((0.5 - h_k) * (d(X,A) - d(X,B)) + (U_k - V_k)) + 0.25 * (d(Y_k,B) + d(C_k,B))) - (0.5 * h_k) * (d(A,B) + d(X,B)).
+ *   Non-finite values are computed with like any other; a NaN gain is no target's gain.
+ * Best target of X: the greatest gain, then the smaller w, over the targets whose gain is not NaN.  X is a candidate iff that
+ *   gain is > 0.
+ * Selection.  The candidates in the order (gain descending, d ascending); one is selected iff its node set {x0, a0, q,
+ *   p_1 .. p_k, b0} shares no node with that of a candidate selected before it.
+ * Round.  All selected moves are applied (node ids never change), the tree is hung from t0 again (c0(v) < c1(v) by id) and
+ *   evaluated.  L' < L: accepted.  Otherwise the round is discarded and the first candidate alone is applied -- a fallback,
+ *   counted whether or not it is accepted -- and accepted if L' < L; if not, the search ends on the tree it had.  It also ends
+ *   with no candidate, or after max_rounds accepted rounds.  max_rounds = 0: the outputs of dpr_bme_nni(.., 0, ..). */
+/* On the device.  Preconditions, errors, table and outputs as dpr_bme_nni (the context's table is shared: a call after a
+ * dpr_bme_nni over no fewer tips allocates no table); the scan's own buffers -- among them one of traversal stacks sized by the
+ * resident scan threads, not by n -- are allocated by the first call and kept.  stats6: accepted rounds, moves applied in them,
+ * fallbacks, candidates of the input tree, applied moves with k >= 2, the largest k applied. */
+int dpr_bme_spr(dpr_ctx *ctx, int64_t n, const int32_t *merge_x, const int32_t *merge_y, int max_rounds, int32_t *kids, int32_t *top,
+                double *len, double *L_rounds, int64_t *stats6);
+/* host only, no GPU: the whole loop restated -- the reference of the GPU tests */
+int dpr_bme_spr_host(const double *lower_rows, int64_t n, const int32_t *merge_x, const int32_t *merge_y, int max_rounds, int32_t *kids,
+                     int32_t *top, double *len, double *L_rounds, int64_t *stats6);
+/* host only (test hooks).  One scan of the tree (kids, top): per directed subtree d (2 (2n-2) entries each) the gain, target w
+ * and path length k of its best target -- gain 0, w -1, k 0 where d is not prunable or has no target with a gain -- and L. */
+int dpr_bme_spr_eval_host(const double *lower_rows, int64_t n, const int32_t *kids, int32_t top, double *best_gain, int32_t *best_w,
+                          int32_t *best_k, double *L);
+/* the gain and path length of the one move (d, w), NaN included; DPR_ERR_ARG if w is no target of d */
+int dpr_bme_spr_gain_host(const double *lower_rows, int64_t n, const int32_t *kids, int32_t top, int64_t d, int32_t w, double *gain,
+                          int32_t *k);
+/* of the last dpr_bme_spr, summed over its evaluations (HIP events): mirror, scan, best of both sides and their copy back;
+ * dpr_get_bme_timing gives the table and the lengths of the same call */
+int dpr_get_bme_spr_timing(dpr_ctx *ctx, double *scan_ms);
+/* out4: bytes of the traversal stacks, device allocations dpr_bme_spr has made for this context beyond the table's, scan
+ * launches of its last call, resident scan threads the stacks are sized for */
+int dpr_get_bme_spr_stats(dpr_ctx *ctx, int64_t *out4);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
