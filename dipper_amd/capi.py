@@ -166,6 +166,11 @@ def load_library():
     L.dpr_bme_spr_gain_host.argtypes = [c_f64p, C.c_int64, c_i32p, C.c_int32, C.c_int64, C.c_int32, c_f64p, c_i32p]
     L.dpr_get_bme_spr_timing.argtypes = [C.c_void_p, c_f64p]
     L.dpr_get_bme_spr_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_upgma_run.argtypes = [C.c_void_p, C.c_int, c_i32p, c_i32p, c_f64p]
+    L.dpr_upgma_run.restype = C.c_int64
+    L.dpr_upgma_host.argtypes = [c_f64p, C.c_int64, C.c_int, c_i32p, c_i32p, c_f64p]
+    L.dpr_get_upgma_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_get_upgma_timing.argtypes = [C.c_void_p, c_f64p]
     L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
     L.dpr_transfer_taxa.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
@@ -456,6 +461,18 @@ def bme_spr_gain_host(D, kids, top, d, w):
 
 
 NJ_VARIANT_NJ, NJ_VARIANT_BIONJ = 0, 1
+
+
+def upgma_host(D, linkage=0):
+    """UPGMA (linkage 0) or WPGMA (1) restated naively on the host (no GPU).  D: (n, n) array whose strict lower triangle is read.
+    dict(merge_x, merge_y, height), n - 1 entries each: the slots merged (the first n - 2 entries are an NJ-style merge log, the
+    last one is the root) and the height of the node n + it they make"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    cnt = max(n - 1, 1)
+    mx, my, h = np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.float64)
+    _chk(lib, lib.dpr_upgma_host(_p(rows, c_f64p), n, int(linkage), _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p)))
+    return dict(merge_x=mx[: n - 1], merge_y=my[: n - 1], height=h[: n - 1])
 
 
 def nj_variant_host(variant, D, max_iters=-1):
@@ -964,6 +981,29 @@ class Dipper:
         out = np.zeros(4, dtype=np.int64)
         _chk(self.L, self.L.dpr_get_bme_stats(self.h, _p(out, c_i64p)))
         return dict(table_bytes=int(out[0]), allocations=int(out[1]), launches=int(out[2]), evaluations=int(out[3]))
+
+    def upgma(self, linkage=0):
+        """upgma_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run); the
+        context's matrix is left as it was"""
+        n = self.n_total()
+        cnt = max(n - 1, 1)
+        mx, my, h = np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.float64)
+        done = self.L.dpr_upgma_run(self.h, int(linkage), _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p))
+        if done < 0:
+            _chk(self.L, int(done))
+        return dict(merge_x=mx[:done], merge_y=my[:done], height=h[:done])
+
+    def upgma_stats(self):
+        """dict(bytes held, allocations so far, launches and rows rescanned of the last upgma)"""
+        out = np.zeros(4, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_upgma_stats(self.h, _p(out, c_i64p)))
+        return dict(bytes=int(out[0]), allocations=int(out[1]), launches=int(out[2]), rescanned=int(out[3]))
+
+    def upgma_timing(self):
+        """ms of the n - 1 iterations of the last upgma (HIP events)"""
+        a = C.c_double()
+        _chk(self.L, self.L.dpr_get_upgma_timing(self.h, C.byref(a)))
+        return a.value
 
     def transfer_taxa(self, n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi_sum=None, moved=None, pairs=None):
         """transfer_taxa_host's numbers, computed on the device"""

@@ -62,6 +62,7 @@ struct dpr_ctx {
     double pfix_ms[2] = { 0, 0 };    // distance blocks, scan + reduce of the last dpr_place_fixed_run
     dpr::TbeBuffers tbe;
     dpr::BmeBuffers bme;             // dpr_bme_nni: the table of subtree averages and its small arrays
+    dpr::UpgmaBuffers upgma;         // dpr_upgma_run: the working copy of the matrix, the nearest-neighbour cache and the log
     int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip
     double* packed_lower = nullptr;  // MATRIX source, device

@@ -473,6 +473,23 @@ struct BmeBuffers {
     double spr_scan_ms = 0;              // of the last dpr_bme_spr: mirror, scan, best and their copy back (HIP events)
 };
 
+// ---- UPGMA / WPGMA (upgma.hip) ---------------------------------------------------------------------------------------------------
+// Kept by the context from the first dpr_upgma_run on (a later call over no more tips allocates nothing); released with it.
+struct UpgmaBuffers {
+    DevBuf<double> D;                    // [cap_n][ld] working copy of the matrix, both triangles
+    DevBuf<double> size;                 // [cap_n] tips under every active slot
+    DevBuf<uint64_t> nkey;               // [cap_n] nearest neighbour of every active row: key of its distance ...
+    DevBuf<int32_t> nn;                  // ... and its slot
+    DevBuf<int32_t> list;                // [cap_n] rows to scan again this iteration
+    DevBuf<int32_t> log_x, log_y;        // [cap_n] the merge log
+    DevBuf<double> log_h;                // [cap_n] height of every merge
+    DevBuf<char> st;                     // the loop's state (UpgmaState)
+    int64_t cap_n = 0, ld = 0;           // tips the buffers hold, row stride of D
+    int64_t allocations = 0;             // device allocations made for this context so far
+    int64_t launches = 0, rescanned = 0; // of the last call: kernels, rows scanned again
+    double loop_ms = 0;                  // of the last call: the n - 1 iterations (HIP events)
+};
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of 512 tips the (value -> tips, positions) postings
 struct MashIndex {

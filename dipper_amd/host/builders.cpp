@@ -18,6 +18,12 @@ bool& bionjOption()
     return on;
 }
 
+int& upgmaOption()
+{
+    static int linkage = -1;
+    return linkage;
+}
+
 DeviceContext::DeviceContext(int device)
 {
     gpuCheck(dpr_create(&ctx, device), "dpr_create");
@@ -208,6 +214,24 @@ void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<st
         std::cerr << "  device: distances " << dist_ms << " ms, NJ " << nj_ms << " ms; dpr_nj_run call "
                   << std::chrono::duration<double, std::milli>(t1 - t0).count() << " ms; Newick text "
                   << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() << " ms\n";
+    }
+}
+
+void NJDeviceArrays::findUpgmaTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_, int linkage)
+{
+    const int N = d_numSequences;
+    std::vector<int32_t> mx((size_t)(N - 1)), my((size_t)(N - 1));
+    std::vector<double> h((size_t)(N - 1));
+    const int64_t done = dpr_upgma_run(dev.ctx, linkage, mx.data(), my.data(), h.data());
+    if (done < 0) gpuCheck((int)done, "dpr_upgma_run");
+    writeNewickFromUpgma(output_, name, mx, my, h);
+    int64_t stats[4] = { 0, 0, 0, 0 };
+    dpr_get_upgma_stats(dev.ctx, stats);
+    std::cerr << (linkage ? "WPGMA: " : "UPGMA: ") << N << " tips, root height " << h[(size_t)(N - 2)] << ", " << stats[3] << " rows rescanned\n";
+    if (cliLog()) {
+        double loop_ms = 0;
+        dpr_get_upgma_timing(dev.ctx, &loop_ms);
+        std::cerr << "  device: " << (linkage ? "WPGMA" : "UPGMA") << " loop " << loop_ms << " ms, " << stats[2] << " launches\n";
     }
 }
 

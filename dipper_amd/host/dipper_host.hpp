@@ -131,6 +131,9 @@ void printRankSummary(dpr_ctx* ctx);
 
 // --bionj: every context this command creates builds BIONJ trees (dpr_ctx_set_nj_variant); set by main() before the first one
 bool& bionjOption();
+// --upgma (0) / --wpgma (1): the linkage every tree of this command is clustered with (dpr_upgma_run in place of dpr_nj_run);
+// -1 = NJ.  Set by main() before the first tree
+int& upgmaOption();
 
 struct DeviceContext {  // replaces cudaSetDevice (src/tree_generation.cu:240-245)
     dpr_ctx* ctx = nullptr;
@@ -170,6 +173,8 @@ struct NJDeviceArrays {  // src/mash_placement.cuh:199-212
     // --nni R: the NJ / BIONJ tree as above, the distance matrix built again, at most R rounds of balanced minimum evolution NNI
     // on it (dpr_bme_nni) and the tree it ends on with its balanced branch lengths; one line on stderr.  spr (--spr R): the SPR
     // search of dpr_bme_spr in its place
+    // --upgma / --wpgma: the rooted tree of dpr_upgma_run on the matrix getDismatrix built; one line on stderr
+    void findUpgmaTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_, int linkage);
     void findRefinedTree(DeviceContext& dev, Param& params, MatrixReader* matrixReader, std::vector<std::string>& name, std::ostream& output_,
                          int rounds, bool spr = false);
 };
@@ -283,6 +288,12 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
 // every node; the root joins name[N-1] and `top`, each with half of len[top], as the NJ writer halves its last edge
 void writeNewickFromKids(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& kid, int32_t top,
                          const std::vector<double>& len);
+
+// Rooted Newick text `(A:l,B:l);` of a UPGMA / WPGMA log (dpr_upgma_run: N-1 merges with the realID bookkeeping of the NJ log, the
+// last one the root; h the height of every new node): a child's branch is its parent's height minus its own, as it comes.
+// labels as writeNewickFromMerges (internal nodes N+k, k < N-2; the root carries none).
+void writeNewickFromUpgma(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
+                          const std::vector<int32_t>& my, const std::vector<double>& h, const std::vector<int32_t>* labels = nullptr);
 
 // ---- bootstrap support (support.cpp; no reference counterpart) -----------------------------------------------------------
 struct BootstrapOptions {

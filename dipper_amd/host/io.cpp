@@ -688,6 +688,25 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
     writeBinaryNewick(os, name, kids, root, labels);
 }
 
+void writeNewickFromUpgma(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
+                          const std::vector<int32_t>& my, const std::vector<double>& h, const std::vector<int32_t>* labels)
+{
+    const int N = (int)name.size();
+    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });
+    std::vector<int> realID((size_t)N);
+    std::vector<double> height((size_t)N, 0.0);
+    for (int i = 0; i < N; ++i) realID[(size_t)i] = i;
+    for (int it = 0; it < N - 1; ++it) {      // merge it makes node N + it; the last one, 2N - 2, is the root
+        const int x = mx[(size_t)it], y = my[(size_t)it], last = N - it - 1;
+        const double hnew = h[(size_t)it];
+        kids[(size_t)(N + it) * 2] = Child{ realID[(size_t)x], hnew - height[(size_t)x] };
+        kids[(size_t)(N + it) * 2 + 1] = Child{ realID[(size_t)y], hnew - height[(size_t)y] };
+        realID[(size_t)x] = N + it; height[(size_t)x] = hnew;
+        realID[(size_t)y] = realID[(size_t)last]; height[(size_t)y] = height[(size_t)last];
+    }
+    writeBinaryNewick(os, name, kids, 2 * N - 2, labels);
+}
+
 void writeNewickFromKids(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& kid, int32_t top,
                          const std::vector<double>& len)
 {

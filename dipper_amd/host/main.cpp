@@ -100,6 +100,15 @@ static const char* kHelp =
     "                              which leaves optima that hold --nni.  At most arg >= 0 rounds, each applying\n"
     "                              every improving move that shares no node with a better one.  Valid where\n"
     "                              --nni is; not together with --nni\n"
+    "  --upgma                     Build a rooted, ultrametric tree by UPGMA (average linkage: the distance of two\n"
+    "                              clusters is the mean over their pairs of tips) instead of NJ; the tree is\n"
+    "                              written rooted, `(A:l,B:l);`, every tip at the same distance from the root.\n"
+    "                              Wherever conventional NJ builds the tree (-m 2, or -m 0 below 30000; -i d,\n"
+    "                              m or r; --protein; every -d); one GPU; with --bootstrap the main tree and\n"
+    "                              every replicate tree are UPGMA trees.  Not with --bionj, --nni, --spr,\n"
+    "                              -m 1, -m 3, --add, -o d, -o j or several ranks\n"
+    "  --wpgma                     As --upgma with WPGMA: a merged cluster's distances are the plain mean of\n"
+    "                              its two parts' (McQuitty's weighted linkage).  Not together with --upgma\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -128,7 +137,7 @@ static const Opt kOpts[] = {
     { "rank", 0, true }, { "world", 0, true }, { "rendezvous", 0, true }, { "dump-tree", 0, true }, { "dump-fasta", 0, false }, { "dump-lengths", 0, false }, { "dump-packed", 0, true }, { "dump-jplace", 0, true },
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
-    { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true },
+    { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
 };
 
 static void usageError(const std::string& what)
@@ -330,6 +339,19 @@ int main(int argc, char** argv)
         if (out == "d" || out == "j") usageError(refine + " needs tree output (-o t)");
         if (vm.count("bootstrap")) usageError(refine + " is not supported with --bootstrap (replicate trees are not refined)");
     }
+    // --upgma / --wpgma: what the arguments alone decide, before any input is read or a GPU touched (several ranks: below)
+    const int upgma = vm.count("upgma") ? 0 : vm.count("wpgma") ? 1 : -1;      // the linkage, -1 = NJ
+    const std::string cluster = upgma == 1 ? "--wpgma" : "--upgma";
+    if (upgma >= 0) {
+        const std::string al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
+        if (vm.count("upgma") && vm.count("wpgma")) usageError("--upgma is not supported with --wpgma (one linkage a tree)");
+        if (bionj) usageError(cluster + " is not supported with --bionj (it builds the tree in place of NJ / BIONJ)");
+        if (vm.count("nni") || spr) usageError(cluster + " is not supported with " + refine + " (a rooted ultrametric tree is not refined)");
+        if (al == "1" || al == "3") usageError(cluster + " builds the tree where conventional NJ does (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add")) usageError(cluster + " is not supported with --add");
+        if (out == "d" || out == "j") usageError(cluster + " needs tree output (-o t)");
+        upgmaOption() = upgma;
+    }
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
     // --protein: what the arguments alone decide, before any input is read or a GPU touched
@@ -450,6 +472,8 @@ int main(int argc, char** argv)
     const bool multi = ranks.multi();
     if (nni >= 0 && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
         usageError(refine + " runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
+    if (upgma >= 0 && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
+        usageError(cluster + " runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
     if (!multi && ranks.devices.size() == 1) device = ranks.devices[0];      // (`--devices 3` alone: one rank on GPU 3)
 
     const int placement_thr = 30000, dc_thr = 1000000;  // src/tree_generation.cu:247-248
@@ -695,6 +719,9 @@ int main(int argc, char** argv)
         if (nni >= 0 && pick_mode((long long)numSequences) != 2)
             die("ERROR: " + refine + " needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (upgma >= 0 && pick_mode((long long)numSequences) != 2)
+            die("ERROR: " + cluster + " builds the tree where conventional NJ does: " + std::to_string(numSequences) + " sequences select " +
+                (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (protein && pick_mode((long long)numSequences) == 3)
             die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
                 " sequences select it in the default mode; use -m 1 or -m 2");
@@ -761,9 +788,10 @@ int main(int argc, char** argv)
             kplacementDeviceArrays.printTree(names, *output_);
             std::cerr << "Tree Created in: " << tree_ms << " ms\n";
         } else {
-            std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
+            if (upgma >= 0) std::cerr << "Using " << (upgma ? "WPGMA" : "UPGMA") << "\n";
+            else std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
             if (numSequences >= 40000)
-                std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
+                std::cerr << "Warning: forcing " << (upgma >= 0 ? "UPGMA / WPGMA" : "conventional NJ") << " on large datasets might result in unexpected behavior\n";
             auto t0 = std::chrono::high_resolution_clock::now();
             NJDeviceArrays njDeviceArrays;
             njDeviceArrays.getDismatrix(dev, (int)numSequences, params, nullptr);
@@ -777,6 +805,8 @@ int main(int argc, char** argv)
                                               seqLen, names, *output_);
             } else if (nni >= 0) {
                 njDeviceArrays.findRefinedTree(dev, params, nullptr, names, *output_, nni, spr);
+            } else if (upgma >= 0) {
+                njDeviceArrays.findUpgmaTree(dev, names, *output_, upgma);
             } else {
                 njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
             }
@@ -810,6 +840,9 @@ int main(int argc, char** argv)
         if (nni >= 0 && mode != 2)
             die("ERROR: " + refine + " needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
                 (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (upgma >= 0 && mode != 2)
+            die("ERROR: " + cluster + " builds the tree where conventional NJ does: " + std::to_string(numSequences) + " sequences select " +
+                (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (mode == 3) { std::cerr << "Divide-and-conquer mode not supported with input matrix\n"; return 1; }
         if (multi) startRanks(ranks, device);
         auto output_ = open_out();
@@ -823,12 +856,14 @@ int main(int argc, char** argv)
             kplacementDeviceArrays.findPlacementTree(dev, params);
             kplacementDeviceArrays.printTree(matrixReader.name, *output_);
         } else {
-            std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
+            if (upgma >= 0) std::cerr << "Using " << (upgma ? "WPGMA" : "UPGMA") << "\n";
+            else std::cerr << "Using conventional NJ" << (bionj ? " (BIONJ)" : "") << "\n";
             if (numSequences >= 40000)
-                std::cerr << "Warning: forcing conventional NJ on large datasets might result in unexpected behavior\n";
+                std::cerr << "Warning: forcing " << (upgma >= 0 ? "UPGMA / WPGMA" : "conventional NJ") << " on large datasets might result in unexpected behavior\n";
             NJDeviceArrays njDeviceArrays;
             njDeviceArrays.getDismatrix(dev, numSequences, params, &matrixReader);
             if (nni >= 0) njDeviceArrays.findRefinedTree(dev, params, &matrixReader, matrixReader.name, *output_, nni, spr);
+            else if (upgma >= 0) njDeviceArrays.findUpgmaTree(dev, matrixReader.name, *output_, upgma);
             else njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_);
         }
         printRankSummary(dev.ctx);

@@ -11,6 +11,8 @@
 // --bootstrap-taxa FILE: dpr_transfer_taxa (device) per replicate -- in place of dpr_transfer_support with tbe, next to
 // dpr_split_support with fbp -- adds to moved[tip] and pairs; one more 64-bit sum over the ranks; rank 0 writes FILE.  The report's
 // tips are numbered in input order, so that call gets the trees with the tips renamed from slots to input indices (relabelledLog).
+// --upgma / --wpgma (one rank): dpr_upgma_run in place of every dpr_nj_run; the first n - 2 entries of its log are a merge log of the
+// same unrooted tree and go to the support functions unchanged, the whole log to writeNewickFromUpgma (the root carries no label).
 #include "dipper_host.hpp"
 
 #include <algorithm>
@@ -122,7 +124,21 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
     std::vector<int32_t> mx((size_t)k), my((size_t)k);
     std::vector<double> bx((size_t)k), by((size_t)k);
     double last = 0.0;
-    const int64_t done = dpr_nj_run(dev.ctx, -1, mx.data(), my.data(), bx.data(), by.data(), &last);
+    // --upgma / --wpgma: every tree by dpr_upgma_run; the first n - 2 entries of its log are the unrooted tree everything below counts on
+    const int linkage = upgmaOption();
+    std::vector<int32_t> ux((size_t)(linkage >= 0 ? n - 1 : 0)), uy(ux.size()), urx(ux.size()), ury(ux.size());
+    std::vector<double> uh(ux.size()), urh(ux.size());
+    int64_t rescanned = 0;
+    if (linkage >= 0) {
+        const int64_t udone = dpr_upgma_run(dev.ctx, linkage, ux.data(), uy.data(), uh.data());
+        if (udone < 0) gpuCheck((int)udone, "dpr_upgma_run");
+        std::copy(ux.begin(), ux.begin() + (std::ptrdiff_t)(n - 2), mx.begin());
+        std::copy(uy.begin(), uy.begin() + (std::ptrdiff_t)(n - 2), my.begin());
+        int64_t stats[4] = { 0, 0, 0, 0 };
+        dpr_get_upgma_stats(dev.ctx, stats);
+        rescanned = stats[3];
+    }
+    const int64_t done = linkage >= 0 ? n - 2 : dpr_nj_run(dev.ctx, -1, mx.data(), my.data(), bx.data(), by.data(), &last);
     if (done < 0) gpuCheck((int)done, "dpr_nj_run");
     if (cliLog()) {
         double dist_ms = 0, nj_ms = 0;
@@ -166,8 +182,16 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
         if (int rc = dpr_dist_matrix(rctx, DPR_SRC_MSA, (int)params.distanceType, 0)) fail(r, "dpr_dist_matrix", rc);
         const auto t2 = Clock::now();
         double rlast = 0.0;
-        const int64_t rdone = dpr_nj_run(rctx, -1, rx.data(), ry.data(), rbx.data(), rby.data(), &rlast);
-        if (rdone < 0) fail(r, "dpr_nj_run", (int)rdone);
+        int64_t rdone;
+        if (linkage >= 0) {
+            rdone = dpr_upgma_run(rctx, linkage, urx.data(), ury.data(), urh.data());
+            if (rdone < 0) fail(r, "dpr_upgma_run", (int)rdone);
+            std::copy(urx.begin(), urx.begin() + (std::ptrdiff_t)(n - 2), rx.begin());
+            std::copy(ury.begin(), ury.begin() + (std::ptrdiff_t)(n - 2), ry.begin());
+        } else {
+            rdone = dpr_nj_run(rctx, -1, rx.data(), ry.data(), rbx.data(), rby.data(), &rlast);
+            if (rdone < 0) fail(r, "dpr_nj_run", (int)rdone);
+        }
         const auto t3 = Clock::now();
         if (bo.taxa) {
             relabelledLog(n, rx, ry, inputOf, irx, iry);
@@ -202,7 +226,12 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
 
     const std::vector<int32_t> labels = bo.tbe ? transferLabels(n, mx, my, phi_sum, bo.replicates)
                                                : supportLabels(n, mx, my, counts, bo.replicates);
-    writeNewickFromMerges(output_, name, mx, my, bx, by, last, &labels);
+    if (linkage >= 0) {
+        writeNewickFromUpgma(output_, name, ux, uy, uh, &labels);
+        std::cerr << (linkage ? "WPGMA: " : "UPGMA: ") << n << " tips, root height " << uh[(size_t)(n - 2)] << ", " << rescanned << " rows rescanned\n";
+    } else {
+        writeNewickFromMerges(output_, name, mx, my, bx, by, last, &labels);
+    }
     std::cerr << "Bootstrap: " << bo.replicates << " replicates (seed " << bo.seed << ") in " << (long long)ms(tb0, tb1) << " ms, "
               << (mine ? mine_ms / (double)mine : 0.0) << " ms per replicate, " << ri.world << " ranks"
               << (bo.tbe ? ", metric tbe (transfer bootstrap expectation)" : "") << "\n";

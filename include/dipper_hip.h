@@ -680,6 +680,43 @@ int dpr_get_bme_spr_timing(dpr_ctx *ctx, double *scan_ms);
  * launches of its last call, resident scan threads the stacks are sized for */
 int dpr_get_bme_spr_stats(dpr_ctx *ctx, int64_t *out4);
 
+/* ---- UPGMA / WPGMA: average-linkage clustering, the rooted and ultrametric distance method (Sokal & Michener 1958; no reference
+ * counterpart: the reference builds unrooted NJ trees only) ---------------------------------------------------------------------
+ * Arithmetic contract (fp64, exactly this order of operations, no contraction; the device and dpr_upgma_host produce the same
+ * bits).
+ * State.  n slots and a symmetric matrix D whose diagonal is never read; sizes s[k] = 1.0 (doubles), heights h[k] = 0.0,
+ *   real[k] = k.  Iteration it = 0 .. n-2 works on the m = n - it active slots.
+ * Order of values.  key(v) is an unsigned 64-bit integer: all ones for a NaN; otherwise, b being the bits of v with +0.0 taken
+ *   for -0.0, ~b if the sign bit is set, else b | 2^63.  So negative < zero < positive finite < +inf < NaN.
+ * Selection.  The pair 0 <= i < j < m with the smallest (key(D[j][i]), i, j), compared lexicographically.  A pair always exists
+ *   for m >= 2: a run does n - 1 merges whatever the matrix holds, +inf and NaN pairs last.
+ * Merge.  x = i, y = j, d = D[y][x]; hnew = 0.5 * d; the log gets merge_x[it] = x, merge_y[it] = y, height[it] = hnew.  The new
+ *   node is n + it, its children real[x] and real[y], their branch lengths hnew - h[x] and hnew - h[y] as they come: nothing is
+ *   clamped.
+ * Update.  For every active k other than x and y, a = D[x][k], b = D[y][k]:
+ *   linkage 0 (UPGMA): val = (s[x] * a + s[y] * b) / (s[x] + s[y]);     linkage 1 (WPGMA): val = 0.5 * (a + b);
+ *   D[x][k] = D[k][x] = val.  Then s[x] = s[x] + s[y], h[x] = hnew, real[x] = n + it.
+ * Slot move (NJ's realID bookkeeping).  If y != m-1, slot m-1 moves to y: row, column, s, h and real.  The first n - 2 log
+ *   entries are therefore a merge log as dpr_nj_run writes it (0 <= x < y < n - it) and describe the same unrooted tree; the last
+ *   entry is always (0, 1) and makes the root. */
+/* On the device (upgma.hip).  Reads the context's FRESH matrix -- after dpr_dist_matrix, before any NJ iteration, in whatever
+ * layout the context's NJ plan gave it -- else DPR_ERR_STATE.  n < 2, a linkage other than 0 / 1, several ranks, virtual ranks
+ * or virtual shards: DPR_ERR_ARG, and the context stays usable.  Works on a square fp64 copy that the context owns (7.2 GB at
+ * 30 000 tips) and frees with itself; one that does not fit the device's free memory is DPR_ERR_ARG with the bytes needed in the
+ * message.  A later call over no more tips allocates nothing.  The context's own matrix is left as it was: a dpr_nj_run after
+ * this call gives the merge log it would have given without it.  merge_x, merge_y, height: n - 1 entries each.  Returns the
+ * merges done, n - 1, or an error code. */
+int64_t dpr_upgma_run(dpr_ctx *ctx, int linkage, int32_t *merge_x, int32_t *merge_y, double *height);
+/* host only, no GPU: the contract restated naively -- a full scan of the lower triangle per iteration, on purpose not the
+ * device's algorithm (a cache of every row's nearest neighbour) -- the reference of the GPU tests.  lower_rows: the strict
+ * lower triangle row by row, as dpr_set_matrix_lower takes it.  n < 2, a linkage other than 0 / 1, a null pointer: DPR_ERR_ARG. */
+int dpr_upgma_host(const double *lower_rows, int64_t n, int linkage, int32_t *merge_x, int32_t *merge_y, double *height);
+/* out4: bytes the context holds for dpr_upgma_run, device allocations it has made for this context so far, and of its last call
+ * the kernel launches and the rows scanned again for their nearest neighbour (the first fill of the cache not counted) */
+int dpr_get_upgma_stats(dpr_ctx *ctx, int64_t *out4);
+/* of the last dpr_upgma_run: its n - 1 iterations (HIP events; the copy of the matrix and the first fill of the cache are outside) */
+int dpr_get_upgma_timing(dpr_ctx *ctx, double *loop_ms);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
