@@ -3,6 +3,9 @@
 // BIONJ (dpr_ctx_set_nj_variant): always the streaming loop on the rank's own copy; dpr_nj_variant_host restates that loop on the host.
 #include "ctx_internal.hpp"
 
+#include <chrono>
+#include <cstdio>
+
 namespace dpr {
 // NJ algorithm on a single GPU: 1 = exact pruned scan (njp.hip, default), 0 = full streaming scan
 static int g_nj_mode = -1;
@@ -302,23 +305,32 @@ int dpr_reserve_nj(dpr_ctx* c, int64_t n)
     return DPR_OK;
 }
 
-// The first hipGraph of a process costs ~30 ms to instantiate (the next ones 0.2 ms); the pruned NJ replays graphs, so that
-// cost would sit in front of its first 32 iterations with the GPU idle.  The CLI calls this from a helper thread while it
-// reads its input (a private stream: nothing of the context's stream is touched).  Safe to call any number of times.
+// The first hipGraph of a process costs 10-30 ms to instantiate (the next ones 0.2 ms); the pruned NJ replays graphs, so that
+// cost would sit in front of its first 32 iterations with the GPU idle.  The CLI calls this from its device thread, after the
+// allocations and the upload that were waiting for the context.  It runs on the context's own stream and, like every other
+// entry point, must be the only call on its context: a private stream (which let it run beside other calls) is a second
+// hardware queue, 9-16 ms to create, and what ran beside it queued behind the runtime's locks anyway.
+// Safe to call any number of times.
 int dpr_warm_graphs(dpr_ctx* c)
 {
     if (!c) { set_error("dpr_warm_graphs: null ctx"); return DPR_ERR_ARG; }
     DPR_HIP(hipSetDevice(c->device));
-    ScopedStream st;
-    DPR_HIP(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
+    const bool tlog = log_level("cli") > 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (tlog) std::fprintf(stderr, "  dpr_warm_graphs: %s at %.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    };
+    hipStream_t st = c->stream;
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         hipLaunchKernelGGL(dpr_warm_kernel, dim3(1), dim3(64), 0, st, 0);
         ScopedGraph g;
         ScopedGraphExec ge;
         if (hipStreamEndCapture(st, g.put()) == hipSuccess && g) {
             if (hipGraphInstantiate(ge.put(), g, nullptr, nullptr, 0) == hipSuccess && ge) {
+                lap("first hipGraphInstantiate");
                 (void)hipGraphLaunch(ge, st);
                 (void)hipStreamSynchronize(st);
+                lap("graph replayed");
             }
         }
     }
@@ -331,15 +343,15 @@ int dpr_warm_graphs(dpr_ctx* c)
             std::vector<char> h(kWarmBytes);
             (void)hipMemsetAsync(d, 0, kWarmBytes, st);
             (void)hipStreamSynchronize(st);
-            // (on the private stream: a synchronous hipMemcpy runs on the NULL stream, which serialises with every blocking
-            //  stream of the device -- this function may run beside other dpr_* calls of the context; pageable staging is
-            //  exercised all the same)
+            // (asynchronous copies on the context's stream: a synchronous hipMemcpy runs on the NULL stream, which serialises
+            //  with every blocking stream of the device; pageable staging is exercised all the same)
             (void)hipMemcpyAsync(h.data(), d, kWarmBytes, hipMemcpyDeviceToHost, st);
             (void)hipStreamSynchronize(st);
             (void)hipMemcpyAsync(d, h.data(), kWarmBytes, hipMemcpyHostToDevice, st);
             (void)hipStreamSynchronize(st);
         }
     }
+    lap("staged copies both ways");
     (void)hipGetLastError();
     return DPR_OK;
 }

@@ -28,6 +28,10 @@
 // (the band of the (useful, match) table that short alignments use in full).
 #include "dpr_internal.hpp"
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+
 namespace dpr {
 
 constexpr int kKC = 16;   // plane words (32 bases each) staged per step
@@ -781,37 +785,58 @@ __global__ __launch_bounds__(kThreads) void msa_counts_row_kernel(const uint32_t
     match[c] = m;
 }
 
+// The packed array goes to a temporary device buffer in one hipMemcpyAsync and msa_planes_kernel converts it.  Measured against
+// reading the caller's registered array from the kernel and against a pipeline of two pinned chunks: the copy is the fastest
+// of the three at 30 000 x 10 000 and at 550 000 x 1 000 (profiles/msa_upload/variants.jsonl).
 int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hipStream_t s)
 {
+    const bool tlog = log_level("cli") > 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    double last = 0;
+    auto lap = [&](const char* what) {      // (DPR_LOG=cli: every segment ends with a sync of its own, so the laps are the segments)
+        if (!tlog) return;
+        (void)hipStreamSynchronize(s);
+        const double now = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::fprintf(stderr, "  msa_upload: %s %.2f ms (at %.2f)\n", what, now - last, now);
+        last = now;
+    };
     msa_free(m);
     m.n = n; m.L = L; m.W32 = (L + 31) / 32;
     const int64_t W64 = (L + 15) / 16;
+    // every buffer first: no hipMalloc between the launches below
+    int64_t cells = 0;
+    if (L <= kMsaTabSites) cells = (L + 1) * (L + 1);
+    else if (L < (1 << 30) && !std::getenv("DPR_MSA_NO_BAND")) cells = (L + 1) * (kMsaBand + 1);
     DevBuf<uint64_t> d_in;
     DPR_HIP(d_in.alloc((size_t)(n * W64)));
-    DPR_HIP(hipMemcpyAsync(d_in, packed4, sizeof(uint64_t) * (size_t)(n * W64), hipMemcpyHostToDevice, s));
+    lap("d_in allocated");
     DPR_HIP(hipMalloc(&m.planes, sizeof(uint32_t) * (size_t)(4 * n * m.W32)));
+    if (cells) DPR_HIP(hipMalloc(&m.jc_tab, sizeof(double) * (size_t)(2 * cells)));
+    if (!std::getenv("DPR_MSA_NO_FAST"))      // (the switch exists for the A/B runs of profiles/msa_block_bench.py and for the tests)
+        DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)n));
+    lap("planes, table, xstage allocated (3 hipMalloc)");
+    DPR_HIP(hipMemcpyAsync(d_in, packed4, sizeof(uint64_t) * (size_t)(n * W64), hipMemcpyHostToDevice, s));
+    lap("H2D copy");
     const int64_t total = n * m.W32;
     const unsigned grid = (unsigned)((total + kThreads - 1) / kThreads > 8192 ? 8192 : (total + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(msa_planes_kernel, dim3(grid ? grid : 1), dim3(kThreads), 0, s, d_in, n, L, W64,
                        m.W32, m.planes);
     DPR_HIP(hipGetLastError());
+    lap("planes kernel");
     if (L <= kMsaTabSites) {
-        const int64_t cells = (L + 1) * (L + 1);
-        DPR_HIP(hipMalloc(&m.jc_tab, sizeof(double) * (size_t)(2 * cells)));
         hipLaunchKernelGGL(msa_jc_table_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
         DPR_HIP(hipGetLastError());
-    } else if (L < (1 << 30) && !std::getenv("DPR_MSA_NO_BAND")) {
-        const int64_t cells = (L + 1) * (kMsaBand + 1);
-        DPR_HIP(hipMalloc(&m.jc_tab, sizeof(double) * (size_t)(2 * cells)));
+    } else if (cells) {
         hipLaunchKernelGGL(msa_jc_band_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
         DPR_HIP(hipGetLastError());
     }
-    if (!std::getenv("DPR_MSA_NO_FAST")) {      // (the switch exists for the A/B runs of profiles/msa_block_bench.py and for the tests)
-        DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)n));
+    if (m.xstage) {
         hipLaunchKernelGGL(msa_xstage_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, n, m.W32, L, m.xstage);
         DPR_HIP(hipGetLastError());
     }
+    lap("table and xstage kernels");
     DPR_HIP(hipStreamSynchronize(s));      // (d_in is read until here)
+    lap("final sync");
     return DPR_OK;
 }
 

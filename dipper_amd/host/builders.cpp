@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <chrono>
@@ -46,13 +47,22 @@ void printRankSummary(dpr_ctx* ctx)
 }
 
 struct AsyncDeviceContext::Impl {
-    std::thread th, warm;
+    std::thread th;
     DeviceContext* dev = nullptr;
     std::mutex mu;
     std::condition_variable cv;
     size_t reserve_n = 0;
+    const uint64_t* msa_flat = nullptr;      // handed over by uploadMSA
+    size_t msa_n = 0;
+    int msa_len = 0;
+    bool msa_done = false;
     bool closing = false;
     double create_ms = 0;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(const char* what) const
+    {
+        if (cliLog()) std::fprintf(stderr, "  device thread: %s at %.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
 };
 double AsyncDeviceContext::createMs() const { return impl->create_ms; }
 AsyncDeviceContext::AsyncDeviceContext(int device) : impl(new Impl)
@@ -62,14 +72,40 @@ AsyncDeviceContext::AsyncDeviceContext(int device) : impl(new Impl)
         const auto tc0 = std::chrono::steady_clock::now();
         q->dev = new DeviceContext(device);
         q->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count();
-        // (helper of the helper: the one-time graph set-up of the HIP runtime runs beside the allocation below, the uploads
-        //  and the distance kernels; joined when the context goes away)
-        q->warm = std::thread([ctx = q->dev->ctx] { (void)dpr_warm_graphs(ctx); });
+        q->lap("context created");
+        // One thread, one dpr_* call at a time.  What main has handed over goes first, in this order: the NJ matrices (n is
+        // known), the alignment (it is packed); then, once, the graph set-up of the HIP runtime (dpr_warm_graphs, 10-30 ms of
+        // host work inside the runtime).  That warm-up used to run on a thread and a stream of its own; whatever ran beside it
+        // queued behind the runtime's locks -- the upload took 20-60 ms there instead of 5, the distance kernel's launch
+        // waited 25 -- and the private stream alone cost 9-16 ms.
+        bool reserved = false, warmed = false;
         std::unique_lock<std::mutex> lk(q->mu);
-        q->cv.wait(lk, [q] { return q->reserve_n != 0 || q->closing; });
-        const size_t n = q->reserve_n;
-        lk.unlock();
-        if (n) (void)dpr_reserve_nj(q->dev->ctx, (int64_t)n);      // best effort: dpr_dist_matrix allocates what is missing
+        for (;;) {
+            if (q->reserve_n != 0 && !reserved) {
+                const size_t n = q->reserve_n;
+                lk.unlock();
+                (void)dpr_reserve_nj(q->dev->ctx, (int64_t)n);      // best effort: dpr_dist_matrix allocates what is missing
+                q->lap("dpr_reserve_nj done");
+                reserved = true;
+                lk.lock();
+            } else if (q->msa_flat && !q->msa_done) {
+                lk.unlock();
+                gpuCheck(dpr_set_msa(q->dev->ctx, q->msa_flat, (int64_t)q->msa_n, (int64_t)q->msa_len), "dpr_set_msa");
+                q->lap("dpr_set_msa done");
+                lk.lock();
+                q->msa_done = true;
+            } else if (!warmed) {
+                lk.unlock();
+                (void)dpr_warm_graphs(q->dev->ctx);
+                q->lap("dpr_warm_graphs done");
+                warmed = true;
+                lk.lock();
+            } else if (q->closing) {
+                break;
+            } else {
+                q->cv.wait(lk);
+            }
+        }
     });
 }
 void AsyncDeviceContext::reserveNJ(size_t n)
@@ -77,15 +113,19 @@ void AsyncDeviceContext::reserveNJ(size_t n)
     { std::lock_guard<std::mutex> lk(impl->mu); impl->reserve_n = n; }
     impl->cv.notify_all();
 }
+void AsyncDeviceContext::uploadMSA(const PackedSequences& packed)
+{
+    if (packed.numSequences < 2) return;      // (the caller's own checks end the run with their messages)
+    { std::lock_guard<std::mutex> lk(impl->mu); impl->msa_flat = packed.flat.data(); impl->msa_n = packed.numSequences; impl->msa_len = packed.seqLen; }
+    impl->cv.notify_all();
+}
+bool AsyncDeviceContext::msaUploaded() const { return impl->msa_done; }
 DeviceContext& AsyncDeviceContext::get()
 {
     { std::lock_guard<std::mutex> lk(impl->mu); impl->closing = true; }
     impl->cv.notify_all();
     if (impl->th.joinable()) impl->th.join();
-    // the graph warm-up (~30 ms, started when the context came up) is long over when the input has been read; joined here so
-    // that every dpr_* call that follows is the only one on this context (dpr_warm_graphs is the one entry point that may
-    // run beside others -- it touches a private stream only -- and here it ran beside dpr_reserve_nj alone)
-    if (impl->warm.joinable()) impl->warm.join();
+    impl->lap("device thread joined");
     return *impl->dev;
 }
 AsyncDeviceContext::~AsyncDeviceContext()
@@ -93,16 +133,16 @@ AsyncDeviceContext::~AsyncDeviceContext()
     { std::lock_guard<std::mutex> lk(impl->mu); impl->closing = true; }
     impl->cv.notify_all();
     if (impl->th.joinable()) impl->th.join();
-    if (impl->warm.joinable()) impl->warm.join();
     delete impl->dev;
     delete impl;
 }
 
-void MSADeviceArrays::allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed)
+void MSADeviceArrays::allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed, bool uploaded)
 {
     numSequences = packed.numSequences;
     if (numSequences < 2) die("ERROR: need at least two sequences");
     seqLen = packed.seqLen;
+    if (uploaded) return;      // (AsyncDeviceContext::uploadMSA did it on the device thread)
     gpuCheck(dpr_set_msa(dev.ctx, packed.flat.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa");
 }
 

@@ -145,9 +145,14 @@ struct DeviceContext {  // replaces cudaSetDevice (src/tree_generation.cu:240-24
 struct AsyncDeviceContext {
     explicit AsyncDeviceContext(int device);
     ~AsyncDeviceContext();
+    // joins the helper thread: the context exists, what was handed over is done, the graph warm-up (dpr_warm_graphs) has run
     DeviceContext& get();
     // ask the helper thread to allocate the NJ matrices for n tips (dpr_reserve_nj) once the context exists; returns at once
     void reserveNJ(size_t n);
+    // hand the packed alignment to the helper thread: it calls dpr_set_msa once the context exists, after dpr_reserve_nj and
+    // before the graph warm-up; returns at once.  packed must stay as it is until get() has returned
+    void uploadMSA(const PackedSequences& packed);
+    bool msaUploaded() const;      // valid after get(): the alignment is on the device
     // milliseconds dpr_create took on the helper thread (HIP runtime start-up + code object load); valid after get()
     double createMs() const;
 private:
@@ -160,7 +165,8 @@ struct MSADeviceArrays {  // src/mash_placement.cuh:87-98
     int seqLen = 0;
     // seqs[i] goes to slot ids[i]; packs with the 4-bit encoder in parallel and uploads
     void allocateDeviceArrays(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids);
-    void allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed);      // already packed by readSequencesPacked
+    // already packed by readSequencesPacked; uploaded: and on the device already (AsyncDeviceContext::uploadMSA)
+    void allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed, bool uploaded = false);
     // --protein: seqs[i] goes to slot ids[i], one byte per site (dpr_pack_aa), seqLen = length of the sequence in slot 0; a
     // shorter sequence ends in not-a-residue positions
     void allocateDeviceArraysProtein(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids);

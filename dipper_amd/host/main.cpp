@@ -576,6 +576,7 @@ int main(int argc, char** argv)
             [&](const std::vector<std::string>& nd) { return slots_of(nd, nullptr); };
         PackedSequences packed;      // (--protein: the general reader and the per-sequence encoder, as FASTQ)
         if (!protein) readSequencesPacked(inputFile, params.in == "m", -1, packed, nullptr, nullptr, &ids_fn);
+        if (adev && packed.ok && params.in == "m") adev->uploadMSA(packed);      // (one GPU: uploaded by the device thread as soon as the context exists)
         std::vector<std::string> seqs, names;
         std::vector<int> ids;
         if (!packed.ok) {                         // FASTQ: serial parser + the per-sequence encoders
@@ -602,7 +603,7 @@ int main(int argc, char** argv)
             mashDeviceArrays.sketchConstructionOnGpu(dev, params);
         } else {
             MSADeviceArrays msaDeviceArrays;
-            if (packed.ok) msaDeviceArrays.allocateDeviceArrays(dev, packed);
+            if (packed.ok) msaDeviceArrays.allocateDeviceArrays(dev, packed, adev->msaUploaded());
             else if (protein) msaDeviceArrays.allocateDeviceArraysProtein(dev, seqs, ids);
             else msaDeviceArrays.allocateDeviceArrays(dev, seqs, ids);
         }
@@ -697,6 +698,7 @@ int main(int argc, char** argv)
             if (h->adev && n >= 3 && (*h->pick)((long long)n) == 2) h->adev->reserveNJ(n);
         }, &hook);
         const long long parsed_ms = ms_since(inputStart);      // the file is read and packed (host side of the input phase)
+        if (adev && packed.ok && aligned) adev->uploadMSA(packed);      // (one GPU: uploaded by the device thread as soon as the context exists)
         std::vector<std::string> seqs;
         std::vector<int> ids;
         if (!packed.ok) {                         // FASTQ: serial parser + the per-sequence encoders
@@ -740,7 +742,7 @@ int main(int argc, char** argv)
         MashDeviceArrays mashDeviceArrays;
         const int mode = pick_mode((long long)numSequences);
         if (packed.ok) {
-            if (aligned) msaDeviceArrays.allocateDeviceArrays(dev, packed);
+            if (aligned) msaDeviceArrays.allocateDeviceArrays(dev, packed, adev->msaUploaded());
             else mashDeviceArrays.allocateDeviceArrays(dev, packed);
         } else {
             if (protein) msaDeviceArrays.allocateDeviceArraysProtein(dev, seqs, ids);

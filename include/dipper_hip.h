@@ -192,12 +192,13 @@ int dpr_sketch(dpr_ctx *ctx, int k, int S, uint64_t *host_sketches);
  * and calculateU (:94-115).  Builds the (sharded) symmetric fp64 matrix and the row sums U. */
 int dpr_dist_matrix(dpr_ctx *ctx, int source, int dist_type, int k);
 
-/* Pay the one-time costs of the process's first hipGraph instantiation (~30 ms; dpr_nj_run replays graphs) and of its first
- * staged device-to-host copy (~8 ms; the first epoch rebuild of an NJ run reads the row sums back) now, on a private
- * stream -- the CLI calls it from a helper thread while it reads its input.  No reference counterpart.
- * Threading: this is the ONE entry point that may run concurrently with other dpr_* calls on the same context (it
- * touches nothing of the context but its device index; thread-local stream capture, thread-local error string);
- * join the helper thread before dpr_destroy. */
+/* Pay the one-time costs of the process's first hipGraph instantiation (10-30 ms; dpr_nj_run replays graphs) and of its first
+ * staged copies between pageable memory and the device (~9 ms each way unless an upload has paid already; the first epoch
+ * rebuild of an NJ run reads the row sums back) now -- the CLI calls it from its device thread once the allocations and the
+ * upload that waited for the context are done.  No reference counterpart.
+ * Threading: like every other entry point it runs on the context's stream and must be the only call on its context (it
+ * used to run on a private stream, beside other calls: creating that stream cost 9-16 ms, and the calls beside it waited
+ * inside the HIP runtime for as long as they would have waited in a queue). */
 int dpr_warm_graphs(dpr_ctx *ctx);
 
 /* Optional: allocate the matrix buffers of a following dpr_dist_matrix over n tips now (cudaMalloc of the n x n matrix
