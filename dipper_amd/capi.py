@@ -113,6 +113,7 @@ def load_library():
     L.dpr_set_reads.argtypes = [C.c_void_p, c_u64p, c_u64p, c_u64p, C.c_int64]
     L.dpr_set_matrix_lower.argtypes = [C.c_void_p, c_f64p, C.c_int64]
     L.dpr_sketch.argtypes = [C.c_void_p, C.c_int, C.c_int, c_u64p]
+    L.dpr_get_mash_index_info.argtypes = [C.c_void_p, c_i64p]
     L.dpr_dist_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.dpr_reserve_nj.argtypes = [C.c_void_p, C.c_int64]
     L.dpr_warm_graphs.argtypes = [C.c_void_p]
@@ -658,6 +659,13 @@ class Dipper:
         out = np.zeros((n, S), dtype=np.uint64) if fetch else None
         _chk(self.L, self.L.dpr_sketch(self.h, k, S, _p(out, c_u64p) if fetch else None))
         return out
+
+    def mash_index_info(self):
+        """the inverted index of the last sketch call and its kernel's constants (dpr_get_mash_index_info)"""
+        info = np.zeros(8, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_mash_index_info(self.h, _p(info, c_i64p)))
+        names = ("built", "chunk_tips", "chunks", "distinct", "dense", "dense_min", "max_sketch", "beside_task_bound")
+        return {nm: int(v) for nm, v in zip(names, info)}
 
     def kmer_hashes(self, seq, k):
         _, off, lens = self._reads

@@ -266,6 +266,14 @@ int dpr_sketch(dpr_ctx* c, int k, int S, uint64_t* host_sketches)
     return DPR_OK;
 }
 
+int dpr_get_mash_index_info(dpr_ctx* c, int64_t info[8])
+{
+    if (!c || !info) { set_error("dpr_get_mash_index_info: null argument"); return DPR_ERR_ARG; }
+    if (!c->mash.sketches) { set_error("dpr_get_mash_index_info: call dpr_set_reads and dpr_sketch first"); return DPR_ERR_STATE; }
+    mash_index_info(c->mash.index, info);
+    return DPR_OK;
+}
+
 int dpr_get_kmer_hashes(dpr_ctx* c, int64_t seq, int k, const uint64_t* word_off, const uint64_t* len, uint64_t* out)
 {
     if (!c || !c->mash.packed2 || seq < 0 || seq >= c->mash.n || !out || k < 1 || k > 15) { set_error("dpr_get_kmer_hashes: bad argument"); return DPR_ERR_ARG; }

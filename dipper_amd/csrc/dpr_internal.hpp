@@ -491,9 +491,9 @@ struct UpgmaBuffers {
 };
 
 // mash.hip
-// inverted index over the sketches (mash_index.hip): per chunk of 512 tips the (value -> tips, positions) postings
+// inverted index over the sketches (mash_index.hip): per chunk of kIC = 1 024 tips the (value -> tips, positions) postings
 struct MashIndex {
-    uint32_t* post = nullptr;    // [n*S] per chunk sorted by value: 2 * (tip mod 512) << 16 | position; tip 511 + position 65535 = not a first copy
+    uint32_t* post = nullptr;    // [n*S] per chunk sorted by value: 2 * (tip mod kIC) << 16 | position; tip kIC - 1 + position 65535 = not a first copy
     uint64_t* uniq = nullptr;    // [nu] distinct values, chunk after chunk
     uint32_t* off = nullptr;     // [nu + 1] first posting of each distinct value
     uint32_t* bkt = nullptr;     // [chunks][65537] directory on the leading bits: first distinct value of each bucket
@@ -503,7 +503,7 @@ struct MashIndex {
     uint16_t* mult = nullptr;    // [n*S] copies of the value at its first position in a sketch, 0 elsewhere
     double* dtab = nullptr;      // [S + 1] distance of every count
     int32_t* dblk = nullptr;     // [nu] dense block of the value or -1
-    uint16_t* dense = nullptr;   // [ndense][512] position of the value in every tip of the chunk, 65535 = absent
+    uint16_t* dense = nullptr;   // [ndense][kIC] position of the value in every tip of the chunk, 0x7F7F = absent (+ 64 entries of padding)
     int64_t chunks = 0;
     uint32_t nu = 0, ndense = 0;
 };
@@ -538,6 +538,8 @@ int mash_dist_jobs(const MashBuffers& m, const PairJobs& J, int njobs, hipStream
 // mash_index.hip
 int mash_index_build(MashBuffers& m, hipStream_t s);
 void mash_index_free(MashIndex& ix);
+// built, kIC, chunks, nu, ndense, kIDenseMin, largest sketch size, tasks of a launch beside tree kernels above which its grid is bounded
+void mash_index_info(const MashIndex& ix, int64_t info[8]);
 int mash_dist_index(const MashBuffers& m, int64_t r0, int64_t nr, int64_t ncols, double* out, int64_t ld, double* mir,
                     bool transposed, hipStream_t s, int rank, int world);
 // the whole Mash matrix of a rank whose rows are sharded by row blocks (world > 1): D_local holds its rows at full width

@@ -8,17 +8,17 @@
 // ascending order, with three small integers each: the position of v in A, the position of v in B, the multiplicity
 // of v in B -- and one counter.  That is a join, not a merge:
 //   * index (once per sketch set): the tips are cut into chunks of kIC = 1 024; a chunk's (value, tip, position) triples --
-//     first occurrences only -- are sorted by value (round 4: every tip's sketch is already ascending, so a chunk is 512
-//     sorted runs and the sort is nine rounds of pairwise merge-path merges, mi_merge_kernel; until round 3 a rocPRIM
+//     first occurrences only -- are sorted by value (round 4: every tip's sketch is already ascending, so a chunk is kIC
+//     sorted runs and the sort is log2(kIC) = ten rounds of pairwise merge-path merges, mi_merge_kernel; until round 3 a rocPRIM
 //     segmented radix sort -- the one piece of vendor device code near the path, and 3.7 of the library's 5 MB);
 //     per chunk the distinct values, the start of each value's posting list, and a 65 536-bucket directory on the
 //     leading bits;
 //   * query: ONE WAVEFRONT per (row, chunk).  It walks the row's distinct values in ascending order (64 directory
 //     look-ups at a time, one per lane), and for every value found it streams the posting list: lane = posting =
-//     one column tip; counter c[tip] (16 bits, LDS, 1 KiB per wavefront) is read, the reference's condition
+//     one column tip; counter c[tip] (16 bits, LDS, 2 KiB per wavefront) is read, the reference's condition
 //     pos_A + pos_B - c < S tested, c += mult_B stored.  Tips of one posting list are distinct, lists are applied in
 //     value order, so every counter sees its shared values in the reference's order.  At the end c[tip] IS inter.
-//     A value held by most tips of the chunk (every value of a clonal data set) also has a block of 512 positions indexed
+//     A value held by most tips of the chunk (every value of a clonal data set) also has a block of kIC positions indexed
 //     by tip: lanes then read positions and counters in tip order (no address arithmetic, conflict-free LDS).
 // Work per pair = its shared values (550 of 1 000 at 4 % divergence, ~20 for unrelated reads) instead of the ~1 500
 // wave instructions of the table kernel's rank look-ups (68 VALU + 32 LDS wave instructions per pair on clonal reads by
@@ -43,11 +43,15 @@ constexpr int kIC = 1024;            // tips per chunk.  Round 5, with the packe
 constexpr int kIBktLog = 16;
 constexpr int kINB = 1 << kIBktLog;  // directory buckets per chunk
 constexpr int kIThreads = 256;       // (index build kernels)
-// not a first copy: counter of tip 511, position 65535 -- the reference's condition never holds for it (S <= 4096), so the
+// not a first copy: counter of tip kIC - 1, position 65535 -- the reference's condition never holds for it (S <= 4096), so the
 // kernel needs no special case
 constexpr uint32_t kINone = ((uint32_t)(2 * (kIC - 1)) << 16) | 0xFFFFu;
+constexpr int kIMaxSketch = 4096;    // largest sketch size (dpr_sketch refuses more): positions, counters and multiplicities of the packed dense path
+// a launch beside the tree kernels of a placement batch walks its (chunk, row) tasks with this many wavefronts per CU (mash_dist_index)
+constexpr int kIShareWaves = 12;     // (round 5, every batch beside + tree kernels at wave priority 3: 100 000 tips, mean branch 2e-5 / 1e-3:
+                                     //  8: 1.78 / 2.10 s, 12: 1.73 / 2.14, 16: 1.75 / 2.21, 20: 1.76 / 2.28, 24: 2.07 / 2.63)
 
-// payload of every sketch entry: 2 * (tip mod 512) << 16 | position for the first occurrence of a value in its sketch,
+// payload of every sketch entry: 2 * (tip mod kIC) << 16 | position for the first occurrence of a value in its sketch,
 // none for further copies; mult = copies of the value at first occurrences, 0 elsewhere
 __global__ __launch_bounds__(kIThreads) void mi_payload_kernel(const uint64_t* __restrict__ sk, int S, int64_t total,
                                                                uint32_t* __restrict__ pay, uint16_t* __restrict__ mult)
@@ -70,8 +74,8 @@ __global__ __launch_bounds__(kIThreads) void mi_payload_kernel(const uint64_t* _
 
 // ------------------------------------------------------------------------------------------------
 // Index build without vendor device code (round 4).
-// (1) Sort of a chunk's entries by value = MERGE of its 512 runs: a tip's sketch is ascending already.  Round r merges
-//     neighbouring runs of R = S 2^r entries; nine rounds.  One workgroup produces 1 024 consecutive outputs of one pair of
+// (1) Sort of a chunk's entries by value = MERGE of its kIC runs: a tip's sketch is ascending already.  Round r merges
+//     neighbouring runs of R = S 2^r entries; log2(kIC) = ten rounds.  One workgroup produces 1 024 consecutive outputs of one pair of
 //     runs: two merge-path searches on the pair's diagonals find the inputs it needs (<= 1 024 entries, staged in LDS), every
 //     thread then finds its own four outputs by the same search in LDS and merges them serially.  Ties take the LEFT run
 //     first and runs keep their order, i.e. the result is the stable sort of the tip-major input -- what the radix sort gave.
@@ -245,7 +249,7 @@ static int mi_sort_chunks(const uint64_t* sketches, const uint32_t* pay, uint64_
     return DPR_OK;
 }
 
-// head flags of the sorted keys (chunks are fixed segments of 512 S entries)
+// head flags of the sorted keys (chunks are fixed segments of kIC S entries)
 __global__ __launch_bounds__(kIThreads) void mi_heads_kernel(const uint64_t* __restrict__ ks, int64_t total, int64_t seg,
                                                              uint32_t* __restrict__ flag)
 {
@@ -299,7 +303,7 @@ __global__ __launch_bounds__(kIThreads) void mi_buckets_kernel(const uint64_t* _
 }
 
 // Dense values: a value held by at least kIDenseMin tips of a chunk gets, besides its posting list, a block of kIC positions
-// indexed by tip (65535 = absent) -- no larger than the list it replaces in the kernel's inner loop, read in tip order, and the
+// indexed by tip (0x7F7F = absent, mash_index_build's memset) -- no larger than the list it replaces in the kernel's inner loop, read in tip order, and the
 // counters are then touched in tip order too (conflict-free, no address arithmetic).
 constexpr uint32_t kIDenseMin = 3 * kIC / 8;      // (a dense step costs ~7 wave instructions per 128 tips, a posting group ~10 per 64 entries)
 __global__ __launch_bounds__(kIThreads) void mi_dense_flag_kernel(const uint32_t* __restrict__ off, int64_t nu, uint32_t* __restrict__ dflag)
@@ -524,12 +528,25 @@ void mash_index_free(MashIndex& ix)
     ix = MashIndex();
 }
 
+void mash_index_info(const MashIndex& ix, int64_t info[8])
+{
+    const bool built = ix.post != nullptr;
+    info[0] = built ? 1 : 0;
+    info[1] = kIC;
+    info[2] = built ? ix.chunks : 0;
+    info[3] = built ? (int64_t)ix.nu : 0;
+    info[4] = built ? (int64_t)ix.ndense : 0;
+    info[5] = (int64_t)kIDenseMin;
+    info[6] = kIMaxSketch;
+    info[7] = 256ll * kIShareWaves;
+}
+
 int mash_index_build(MashBuffers& m, hipStream_t s)
 {
     mash_index_free(m.index);
     const int S = m.S;
     const int64_t n = m.n, total = n * S;
-    if (S > 4096 || total >= (int64_t)0xFFFF0000ll || n < 2) return DPR_OK;      // not indexable: the other kernels take over
+    if (S > kIMaxSketch || total >= (int64_t)0xFFFF0000ll || n < 2) return DPR_OK;      // not indexable: the other kernels take over
     MashIndex& ix = m.index;
     const int64_t seg = (int64_t)kIC * S, chunks = (n + kIC - 1) / kIC;
     const unsigned gt = (unsigned)((total + kIThreads - 1) / kIThreads);
@@ -546,7 +563,7 @@ int mash_index_build(MashBuffers& m, hipStream_t s)
     DPR_HIP(ks.alloc((size_t)total));
     hipLaunchKernelGGL(mi_payload_kernel, dim3(gt), dim3(kIThreads), 0, s, m.sketches, S, total, pay, ix.mult);
     DPR_HIP(hipGetLastError());
-    // sort every chunk's entries by value: nine rounds of pairwise merges of the (already ascending) sketches
+    // sort every chunk's entries by value: log2(kIC) rounds of pairwise merges of the (already ascending) sketches
     {
         DevBuf<uint64_t> k2;        // merge scratch: released at the end of this block
         DevBuf<uint32_t> p2;
@@ -637,12 +654,10 @@ int mash_dist_index(const MashBuffers& m, int64_t r0, int64_t nr, int64_t ncols,
     int64_t blocks = cchunks * nr;                  // one task per wavefront (a bounded grid walking the tasks: 25 % slower, uneven tasks)
     if (blocks > (int64_t)0x3FFFFFFF) blocks = 0x3FFFFFFF;
     // When tree kernels of a placement batch run beside this launch on another stream (share_chip), the grid is bounded instead:
-    // 12 wavefronts per CU walk the tasks.  A grid of 100 000 small workgroups keeps the dispatcher busy and every wave slot
+    // kIShareWaves = 12 wavefronts per CU walk the tasks.  A grid of 100 000 small workgroups keeps the dispatcher busy and every wave slot
     // taken, and the tree kernels -- 2 launches per tip, up to 1 500 workgroups each -- then make NO progress beside it
     // (100 000 tips: distance 1.2 s + tree 2.0 s = 3.2 s, nothing hidden).
-    constexpr int share_waves = 12;      // (round 5, every batch beside + tree kernels at wave priority 3: 100 000 tips, mean branch 2e-5 / 1e-3:
-                                         //  8: 1.78 / 2.10 s, 12: 1.73 / 2.14, 16: 1.75 / 2.21, 20: 1.76 / 2.28, 24: 2.07 / 2.63)
-    if (m.share_chip && share_waves > 0 && blocks > 256ll * share_waves) blocks = 256ll * share_waves;
+    if (m.share_chip && kIShareWaves > 0 && blocks > 256ll * kIShareWaves) blocks = 256ll * kIShareWaves;
     const size_t pad = 0;
     hipLaunchKernelGGL(mash_dist_index_kernel, dim3((unsigned)blocks), dim3(64), pad, s, ix, m.sketches, m.S, m.n, r0, nr, ncols, cchunks,
                        out, ld, mir, transposed ? 1 : 0, rank, world);

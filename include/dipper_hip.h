@@ -185,6 +185,14 @@ int dpr_set_matrix_lower(dpr_ctx *ctx, const double *rows, int64_t n);
  * S must be 1000 unless the reference quirk of SURVEY 9.8 is lifted; host_sketches (optional)
  * receives [n][S] ascending hashes. */
 int dpr_sketch(dpr_ctx *ctx, int k, int S, uint64_t *host_sketches);
+/* Read-only test hook: the inverted index over the sketches of the last dpr_sketch (the default pair kernel of every unaligned
+ * input) and the constants its kernel is built on.  info[0] built (0 / 1; not built -- DPR_MASH_KERNEL other than auto / index, more
+ * than 2^32 sketch values, no memory -- leaves the counts at 0), info[1] chunk_tips (tips per chunk of columns), info[2] chunks,
+ * info[3] distinct ((chunk, value) pairs = posting lists), info[4] dense (lists with a block of positions by tip), info[5]
+ * dense_min (entries from which a list is dense), info[6] max_sketch (largest sketch size), info[7] beside_task_bound ((chunk, row)
+ * tasks of a placement batch above which its launch beside the tree kernels walks them on a bounded grid).  DPR_ERR_ARG on a null
+ * context or array, DPR_ERR_STATE before dpr_sketch.  No reference counterpart. */
+int dpr_get_mash_index_info(dpr_ctx *ctx, int64_t info[8]);
 
 /* ---- distance matrix: NJDeviceArrays::getDismatrix (src/neighborJoining.cu:35-85) with the row
  * providers MSADeviceArrays/MashDeviceArrays/MatrixReader::distConstructionOnGpu

@@ -73,7 +73,7 @@ def test_mash_dist_matrix_and_nj(gpu, orc):
 @pytest.mark.parametrize("S,k", [(1000, 15), (64, 15), (257, 8), (2000, 15), (5, 4)])
 def test_mash_dist_token_kernel_cases(orc, monkeypatch, S, k, kernel):
     """The three pair kernels -- run-encoded tokens (every sketch as runs of a reference list + literals), inverted
-    index (one wavefront per row x 512 columns, posting lists in value order), bucket tables -- against the oracle's literal
+    index (one wavefront per row x chunk of columns, posting lists in value order), bucket tables -- against the oracle's literal
     loop on the cases their rules have to get right: near-identical reads (long runs, a handful of literals), exact copies,
     reads with repeats (duplicate values: extra copies behind a run, in the reference itself, as literals), short reads
     (padding values = duplicates of the largest value), unrelated reads (all literals) and a reference (sketch 0) that is
@@ -307,25 +307,44 @@ def test_mash_other_sketch_sizes(gpu, orc, S):
     _same_state(got, orc.place_run(M), n)
 
 
+_CHUNK = []
+
+
+def _index_chunk_tips():
+    """tips per chunk of the inverted-index kernel, as the library reports it (Dipper.mash_index_info, after any sketch)"""
+    if not _CHUNK:
+        import dipper_amd
+        d = dipper_amd.Dipper(0)
+        try:
+            d.set_reads([b"ACGTTGCAAC" * 4, b"TTGACCAGTA" * 4])
+            d.sketch(k=8, S=16, fetch=False)
+            _CHUNK.append(d.mash_index_info()["chunk_tips"])
+        finally:
+            d.close()
+    return _CHUNK[0]
+
+
 @pytest.mark.parametrize("S,k", [(300, 15), (1000, 11)])
 def test_mash_index_kernel_several_chunks(orc, monkeypatch, S, k):
-    """The inverted-index kernel over several 512-tip chunks (the last one partial): a clonal clade, a divergent clade,
-    unrelated reads, short reads (padding values) and repeats, in shuffled order; the whole matrix against the oracle's
-    literal loop on a sample of rows that covers every chunk, plus the transposed block of the divide-and-conquer
-    assignment through dc_run's own test elsewhere."""
+    """The inverted-index kernel over more than two chunks of C tips (C = 1 024 since round 5, read from the library; the last
+    chunk partial): a clonal clade, a divergent clade, unrelated reads, short reads (padding values) and repeats, in shuffled
+    order; the whole matrix against the oracle's literal loop on a sample of rows that covers every chunk and both sides of every
+    chunk edge, plus the placement batches.  (The transposed block of the divide-and-conquer assignment over two chunks:
+    tests/test_gpu_mash_index_edges.py.)"""
     import dipper_amd
     from dipper_amd import capi
     monkeypatch.setenv("DPR_MASH_KERNEL", "index")
+    C = _index_chunk_tips()
     rng = np.random.default_rng(S + k)
     L = 1500
-    seqs = _util.synth_reads(rng, 700, L, mean_bl=5e-5, lo=5e-6, hi=5e-4)
-    seqs += _util.synth_reads(rng, 500, L, mean_bl=2e-3, lo=2e-4, hi=2e-2)
+    seqs = _util.synth_reads(rng, 700 * C // 512, L, mean_bl=5e-5, lo=5e-6, hi=5e-4)
+    seqs += _util.synth_reads(rng, 500 * C // 512, L, mean_bl=2e-3, lo=2e-4, hi=2e-2)
     seqs += _reads(rng, 60, 200, 2500, related=False)
     seqs += [seqs[3][:120], b"ACGT" * 12, b"A" * 30, (b"ACGTTGCA" * 30 + seqs[5][:600]) * 2, seqs[10], seqs[10]]
     order = rng.permutation(len(seqs))
     seqs = [seqs[i] for i in order]
     n = len(seqs)
-    assert n > 2 * 512 and n % 512 != 0
+    assert n > 2 * C and n % C != 0
     d = dipper_amd.Dipper(0)
     try:
         d.set_nj_mode(0)
@@ -334,7 +353,9 @@ def test_mash_index_kernel_several_chunks(orc, monkeypatch, S, k):
         d.dist_matrix(capi.SRC_MASH, 0, k)
         M = d.matrix()
         assert np.array_equal(M, M.T) and np.all(np.diag(M) == 0)
-        rows = sorted(set([1, 2, 63, 64, 511, 512, 513, 1023, 1024, 1025, n - 2, n - 1] + list(rng.integers(1, n, size=30))))
+        assert d.mash_index_info()["chunks"] == n // C + 1
+        rows = sorted(set([1, 2, 63, 64, 511, 512, 513, 1023, 1024, 1025, C // 2 - 1, C // 2, C // 2 + 1, C - 1, C, C + 1, 2 * C - 1, 2 * C, 2 * C + 1,
+                           n - 2, n - 1] + list(rng.integers(1, n, size=30))))
         for i in rows:
             ref = orc.mash_dist_row(sk, k, i, i)
             assert np.allclose(M[i, :i], ref, rtol=1e-12, atol=0), (i, np.nonzero(~np.isclose(M[i, :i], ref, rtol=1e-12, atol=0))[0][:5])
@@ -348,9 +369,10 @@ def test_mash_index_kernel_several_chunks(orc, monkeypatch, S, k):
 
 @pytest.mark.parametrize("n,S,k", [(2, 1, 2), (3, 2, 3), (511, 7, 6), (512, 64, 4), (513, 5, 2), (1025, 33, 5)])
 def test_mash_index_kernel_edges(orc, monkeypatch, n, S, k):
-    """Chunk boundaries (one tip short of a chunk, exactly one chunk, one tip over, two chunks + 1), tiny sketches and small
-    k (few distinct hash values: almost every sketch value is a duplicate or a padding value): inverted-index kernel
-    against the oracle's literal loop."""
+    """Tiny sketches and small k (few distinct hash values: almost every sketch value is a duplicate or a padding value) at sizes
+    around half a chunk and at one chunk + 1 tip (chunks of 1 024 tips since round 5; these sizes were the chunk edges of the
+    512-tip kernel): inverted-index kernel against the oracle's literal loop.  One tip short of a chunk, exactly one and the edges of
+    two chunks: tests/test_gpu_mash_index_edges.py::test_chunk_edges."""
     import dipper_amd
     from dipper_amd import capi
     monkeypatch.setenv("DPR_MASH_KERNEL", "index")
@@ -365,7 +387,9 @@ def test_mash_index_kernel_edges(orc, monkeypatch, n, S, k):
         d.dist_matrix(capi.SRC_MASH, 0, k)
         M = d.matrix()
         assert np.array_equal(M, M.T) and np.all(np.diag(M) == 0)
-        rows = range(1, n) if n <= 513 else sorted(set([1, 511, 512, 513, 1023, 1024] + list(rng.integers(1, n, size=40))))
+        C = d.mash_index_info()["chunk_tips"]
+        rows = range(1, n) if n <= 513 else sorted(set([r for r in (1, 511, 512, 513, 1023, 1024, C // 2 - 1, C // 2, C // 2 + 1, C - 1, C) if r < n]
+                                                       + list(rng.integers(1, n, size=40))))
         for i in rows:
             ref = orc.mash_dist_row(sk, k, i, i)
             assert np.allclose(M[i, :i], ref, rtol=1e-12, atol=0), (i, np.nonzero(~np.isclose(M[i, :i], ref, rtol=1e-12, atol=0))[0][:5])
