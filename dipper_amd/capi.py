@@ -149,6 +149,7 @@ def load_library():
     L.dpr_dc_query_share.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dpr_dc_deal_clusters.argtypes = [C.POINTER(C.c_int64), C.c_int64, C.c_int, c_i32p]
     L.dpr_get_dc_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), c_f64p]
+    L.dpr_get_dc_table_stats.argtypes = [C.c_void_p, c_i64p]
     L.dpr_msa_resample.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
     L.dpr_get_msa_boot_weights.argtypes = [C.c_void_p, c_i32p]
     L.dpr_msa_boot_weights.argtypes = [C.c_uint64, C.c_int64, C.c_int64, c_i32p]
@@ -725,6 +726,12 @@ class Dipper:
                              groups=int(counts[3]), jobs=int(counts[4]), backbone_ms=float(ms[0]),
                              assign_ms=float(ms[1]), cluster_ms=float(ms[2])))
         return st
+
+    def dc_table_stats(self):
+        """the assignment table of the last dc_run (dpr_get_dc_table_stats)"""
+        out = np.zeros(4, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_dc_table_stats(self.h, _p(out, c_i64p)))
+        return {nm: int(v) for nm, v in zip(("entries", "chunks", "max_entries", "max_leaves"), out)}
 
     def place_fixed_set(self, m, n, state):
         """dpr_place_fixed_set: the backbone of m tips (adjacency arrays of `state`, sized for n tips) becomes the context's

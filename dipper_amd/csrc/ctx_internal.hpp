@@ -75,6 +75,7 @@ struct dpr_ctx {
     bool place_overlapped = false;      // some batch of the last placement run was produced beside the tree kernels
     int64_t place_batches = 0, place_batches_overlapped = 0;      // of the last placement run
     dpr::DcStats dc_stats;
+    int64_t dc_table_stats[4] = { 0, 0, 0, 0 };      // assignment table of the last dpr_dc_run: entries, chunks, most entries / distinct tips in a chunk
     double dc_ms[3] = { 0, 0, 0 };   // backbone, cluster assignment, cluster trees
     // plan knobs of THIS context (dpr_ctx_set_*); -1 = follow the process-wide default (dpr_set_* / environment)
     int nj_mode = -1, nj_vshards = -1, nj_multi_plan = -1;

@@ -361,6 +361,8 @@ static int dc_assign_queries(DcRun& r)
     const int64_t n = r.n, B = r.B;
     const RowSource src{ c, r.source, r.dist_type };
     if (int rc = dc_table_build(c->place, B, r.tab, c->stream)) return rc;
+    const int64_t ts[4] = { r.tab.nv, r.tab.nch, r.tab.max_entries, r.tab.max_leaves };     // (the table is freed with the run)
+    std::copy(ts, ts + 4, c->dc_table_stats);
     const int64_t Q = query_batch(B, n - B);
     DevBuf<double> dT;      // (released before the budget of the cluster trees is read)
     DPR_HIP(dT.alloc((size_t)(B * Q)));
@@ -498,6 +500,13 @@ int dpr_get_dc_stats(dpr_ctx* c, int64_t* counts5, double* phase_ms3)
         counts5[3] = c->dc_stats.groups; counts5[4] = c->dc_stats.jobs;
     }
     if (phase_ms3) for (int i = 0; i < 3; ++i) phase_ms3[i] = c->dc_ms[i];
+    return DPR_OK;
+}
+
+int dpr_get_dc_table_stats(dpr_ctx* c, int64_t out4[4])
+{
+    if (!c || !out4) { set_error("dpr_get_dc_table_stats: null argument"); return DPR_ERR_ARG; }
+    std::copy(c->dc_table_stats, c->dc_table_stats + 4, out4);
     return DPR_OK;
 }
 

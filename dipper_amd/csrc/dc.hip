@@ -185,6 +185,10 @@ int dc_table_build(PlaceBuffers& p, int64_t B, DcTable& t, hipStream_t s)
         e0v.push_back((int32_t)vs.size());
         l0v.push_back((int32_t)leaf.size());
         t.nch = (int)e0v.size() - 1;
+        for (int c = 0; c < t.nch; ++c) {
+            t.max_entries = std::max(t.max_entries, (int)(e0v[(size_t)c + 1] - e0v[(size_t)c]));
+            t.max_leaves = std::max(t.max_leaves, (int)(l0v[(size_t)c + 1] - l0v[(size_t)c]));
+        }
         if (leaf.empty()) leaf.push_back(0);
         DPR_HIP(hipMalloc(&t.ch_e0, sizeof(int32_t) * e0v.size()));
         DPR_HIP(hipMalloc(&t.ch_l0, sizeof(int32_t) * l0v.size()));

@@ -667,6 +667,7 @@ struct DcTable {
     int32_t* ch_e0 = nullptr;      // [nch + 1] first table entry of a chunk
     int32_t* ch_l0 = nullptr;      // [nch + 1] first entry of a chunk in ch_leaf
     int32_t* ch_leaf = nullptr;    // the chunks' distinct backbone tips
+    int max_entries = 0, max_leaves = 0;      // most table entries / most distinct tips in one chunk (dpr_get_dc_table_stats)
     uint4* et_rec = nullptr;       // [nv][11] x 16 B per entry: for each of the 10 list entries {LDS offset (in doubles) of its staged row (absent: the
                                    // -inf row), 0, path length}; then {slot, 0, edge length} -- copied to LDS per chunk, read there at a wave-uniform address
     double* part_add = nullptr;    // [chunks][ldq] per-chunk first minima

@@ -496,6 +496,11 @@ int dpr_dc_deal_clusters(const int64_t *sizes_desc, int64_t count, int world, in
 /* counts: clusters, largest cluster, in-cluster pair distances, memory groups, pair jobs;
  * phase_ms: backbone tree, cluster assignment, cluster trees (HIP events) */
 int dpr_get_dc_stats(dpr_ctx *ctx, int64_t *counts5, double *phase_ms3);
+/* read-only test hook: the assignment table that the last dpr_dc_run built over its backbone (the table itself is freed with the
+ * run).  out4[0] entries (eligible backbone slots, 2 * backbone - 2), out4[1] chunks of the assignment scan, out4[2] most entries
+ * in one chunk (at most 64), out4[3] most distinct backbone tips named by one chunk's closest lists (at most 48).  Zeros before
+ * the first dpr_dc_run of the context; DPR_ERR_ARG on a null context or array.  No reference counterpart. */
+int dpr_get_dc_table_stats(dpr_ctx *ctx, int64_t out4[4]);
 
 /* ---- independent placement of queries on a FIXED backbone (no reference counterpart: addQuery, src/placement_close_k.cu:
  * 858-990, inserts the queries one after the other; findClustersDC, src/divide_and_conquer/placement_close_k.cu:937-1113,

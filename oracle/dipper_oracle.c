@@ -872,7 +872,7 @@ static int orc_dc_run_phases(int64_t N, int64_t B, const double *dist, int64_t l
     double *dis = (double *)calloc((size_t)N, sizeof(double));        /* d_dist: fresh allocation = 0 */
     int32_t *edge_mask = (int32_t *)malloc(sizeof(int32_t) * (size_t)(4 * N));
     int32_t *mask_index = (int32_t *)malloc(sizeof(int32_t) * (size_t)(4 * N));
-    int32_t *leaf_mask = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * N));
+    int32_t *leaf_mask = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * N + 10));   /* 10 list entries + members (2N alone: too small below 10 tips) */
     int rc = 0;
     /* ---- backbone (findBackboneTreeDC) */
     const int lim_all = (int)(4 * N - 4), lim_bb = (int)(4 * B - 4);
