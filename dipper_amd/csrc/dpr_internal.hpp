@@ -124,7 +124,7 @@ struct NjPruned {
     bool range_known = false;         // t2_hdr holds the range of every entry of this run (njp_range_kernel + the M parts since)
     char* t2_hdr = nullptr; double *t2_rmax = nullptr, *t2_cmax = nullptr, *t2_colmin = nullptr, *t2_rowmin = nullptr, *t2_cmin = nullptr;
     int32_t *slot_of_pos = nullptr, *pos_of_slot = nullptr, *perm = nullptr;   // slot_of_pos < 0: dead position
-    uint64_t* umin = nullptr;   // [strips][groups][4] order-encoded lower bound of D per sub-unit
+    uint64_t* umin = nullptr;   // [strips][groups][4][2] order-encoded lower bound of D per sub-unit and row half (readers take the smaller word)
     int64_t nunits_alloc = 0, utot = 0;
     int64_t utot0 = 0;          // units of one full scan at the first epoch (statistics)
     bool fresh = false;         // epoch just built: the first scan is a full one (njp_list_all_kernel), nothing in quarantine

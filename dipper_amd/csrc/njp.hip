@@ -8,7 +8,8 @@
 //  * the triangle is cut into units of 16 rows x 512 columns, each with four 128-column sub-units (the columns of
 //    one wave of the scan kernel) that carry a lazily maintained lower bound umin[unit][w] <= min D over the
 //    sub-unit (exact whenever it is scanned; lowered by the prep lane that tests the unit when the new node's
-//    row / column crosses it);
+//    row / column crosses it), kept as two words -- one per block that scans the unit, rows 0-7 and 8-15 -- of which every
+//    reader takes the smaller;
 //  * for a unit, every candidate obeys  q = fl(fl(D - Ur_a) - Ur_b) >= fl(fl(umin - rmax) - cmax)
 //    (and the other association order) because fl(x - y) is monotone in x and -y; units whose bound
 //    exceeds a known upper bound of the optimum (the best of the previous iteration's per-block
@@ -233,12 +234,12 @@ __global__ __launch_bounds__(kThreads) void njp_list_all_kernel(NjpArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// SCAN(it).  Blocks [0, ugrid): the listed units -- block b takes entries b, b+G, ... and always writes
-// partials[b] when it had work, so the unit records of a scan are partials[0 .. min(cnt, grid)).  The
+// SCAN(it).  Unit blocks [0, kH x ugrid): the listed units -- block b takes row half b % kH of the entries b / kH, b / kH + G, ...
+// and always writes partials[b] when it had work, so the unit records of a scan are partials[0 .. kH x min(cnt, grid)).  The
 // lane-level best carries the positions of the pair and its distance, so nothing is looked up after the
 // reduction.  The node in quarantine has a NaN row sum: the unit scans skip its row and column (and the
 // exact sub-unit minima they store leave it out).
-// Blocks [0, nrb): the NEW ROW.  They finish the row sum U[x] of the node created by the
+// Blocks [0, nrb), in front of the unit blocks: the NEW ROW.  They finish the row sum U[x] of the node created by the
 // previous merge from the chunk partials (canonical order), evaluate its pairs against every live
 // position from the row buffer, and move the buffered row into the matrix (nobody reads that row validly
 // during this launch); the first of them stores U[x].
@@ -248,7 +249,14 @@ __global__ __launch_bounds__(kThreads) void njp_list_all_kernel(NjpArgs a)
 // kRS (row-sharded mode, njr.hip): D holds this rank's chunks of rows (njp_lrow), only the owner of a position stores its row,
 // the first new-row block adds the rank's header record (the row sum it derived, for the cross-check of the replicated state),
 // and -- mailbox plan -- the last block of the launch to finish pushes the rank's records into every rank's window.
-template <bool kRS>
+// kH (row halves per unit, 1 or 2): a listed unit is scanned by kH blocks of kUR / kH rows each, over all four sub-strips.  Unit
+// block b takes list entry b / kH (then + ugrid, ...) and rows 8 (b % kH) ... of it; the halves share nothing -- no barrier, no
+// LDS step, no hand-over: each writes its own record (the (q, key) reduction of POST does not care about the order or the number
+// of records) and its own word of the sub-unit's bound (umin[unit][w][h]; the readers take the smaller one).  The slowest block
+// sets the length of the launch, and its tail is the key resolution of its tied rows: a half-block holds at most half of them,
+// half of the unrolled pass-2 code and 8 instead of 16 row loads per lane.  The single-GPU loop (unit-sharded included) runs
+// kH = 2, the row-sharded one kH = 1 (its second word holds +inf).
+template <bool kRS, int kH>
 __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const int32_t* h_list, const unsigned long long* h_cnt,
                                                             const double* h_xpart, int h_nrl, NjpArgs a)
 {
@@ -265,7 +273,9 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
     const int nrl = h_nrl;
     const bool unit_block = (int)blockIdx.x >= nrl;
     const int ub = (int)blockIdx.x - nrl;                        // unit block index
-    const int32_t first = unit_block ? h_list[ub] : 0;
+    constexpr int kR = kUR / kH;                                 // rows of a unit block
+    const int ue = ub / kH, uh = ub - ue * kH;                   // its first list entry and its row half
+    const int32_t first = unit_block ? h_list[ue] : 0;
     const double xp0 = unit_block ? 0.0 : h_xpart[tid];          // (the array is padded to a multiple of 256 entries)
     const unsigned long long cl0 = h_cnt[0], cl1 = h_cnt[1], cl2 = h_cnt[2];      // (not a second, dependent load behind `it`)
     // new-row blocks: this thread's two positions of the buffered row (BOTH buffers: which one is current needs `it`) and
@@ -333,7 +343,7 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
         rec_out = a.partials + a.rec_off + ub;
         const int m3 = (int)(it % 3);
         const int64_t cnt = (int64_t)(m3 == 0 ? cl0 : m3 == 1 ? cl1 : cl2);
-        if ((int64_t)ub >= cnt) {
+        if ((int64_t)ue >= cnt) {
             if (a.all_defined && tid == 0) {      // unit-sharded mode: every record of the gathered array is defined
                 if (kRS) njr_store_record(rec_out, 10000.0, ~0ull, 0.0, 0ull);
                 else { NjRecord rec; rec.q = 10000.0; rec.key = ~0ull; rec.d = 0.0; rec.pad = 0ull; *rec_out = rec; }
@@ -349,13 +359,13 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
         // bq is wave-uniform; (bk, bp, bd) is this lane's best candidate AT q == bq (bk == ~0: none).
         int64_t scanned = 0;
         const int wv = tid >> 6;                         // this wave's sub-strip of every unit
-        for (int64_t e = ub; e < cnt; e += a.ugrid, ++scanned) {
-            const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane(e == (int64_t)ub ? first : a.list[e]);
+        for (int64_t e = ue; e < cnt; e += a.ugrid, ++scanned) {
+            const uint32_t code = (uint32_t)__builtin_amdgcn_readfirstlane(e == (int64_t)ue ? first : a.list[e]);
             if (!((code >> (28 + wv)) & 1u)) continue;   // the bound of this wave's sub-unit rules it out (wave-uniform)
             const int cb = (int)((code >> 18) & 1023u);
             const int64_t g_s = (int64_t)(code & 0x3FFFFu);
-            const int64_t c0 = (int64_t)cb * kTileCols, a0 = g_s * kUR;
-            // Rows a0 .. a0+15 are always read: the matrix has a group of rows behind position P and the
+            const int64_t c0 = (int64_t)cb * kTileCols, a0 = g_s * kUR + uh * kR;     // first row of this block's half
+            // Rows a0 .. a0+kR-1 are always read: the matrix has a group of rows behind position P and the
             // vectors carry NaN row sums there (njp_alloc_epoch), so rows >= P behave like dead rows.
             const int64_t b0 = c0 + 2 * tid, b1 = b0 + 1;
             const v2d ubv = *reinterpret_cast<const v2d*>(a.Ur + b0);
@@ -366,21 +376,21 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
             const int64_t ld2 = a.ld >> 1;
             const bool diag = a0 < c0 + kTileCols;
             const bool live0 = ub0 == ub0, live1 = ub1 == ub1;   // dead columns carry NaN row sums
-            v2d v[kUR];
+            v2d v[kR];
 #pragma unroll
-            for (int u8 = 0; u8 < kUR; ++u8) v[u8] = __builtin_nontemporal_load(basep + (int64_t)u8 * ld2);
-            // the 16 rows' row sums and keys: lane l holds row a0 + (l & 15) (three coalesced loads, no scalar-register
+            for (int u8 = 0; u8 < kR; ++u8) v[u8] = __builtin_nontemporal_load(basep + (int64_t)u8 * ld2);
+            // the rows' row sums and keys: lane l holds row a0 + (l & (kR - 1)) (three coalesced loads, no scalar-register
             // pressure); v_readlane hands them out -- the keys only in the rare branch of pass 2
-            const double ua_l = a.Ur[a0 + (tid & 15)];
-            const uint64_t kaa_l = a.KA[a0 + (tid & 15)], kba_l = a.KB[a0 + (tid & 15)];
-            double ua[kUR];
+            const double ua_l = a.Ur[a0 + (tid & (kR - 1))];
+            const uint64_t kaa_l = a.KA[a0 + (tid & (kR - 1))], kba_l = a.KB[a0 + (tid & (kR - 1))];
+            double ua[kR];
 #pragma unroll
-            for (int u8 = 0; u8 < kUR; ++u8) ua[u8] = readlane_f64(ua_l, u8);
+            for (int u8 = 0; u8 < kR; ++u8) ua[u8] = readlane_f64(ua_l, u8);
             NJP_STAMP(0, 1, true);
             if (diag) {   // block-uniform and rare (units on the diagonal): mask the entries with column >= row
                 const int ib0 = (int)b0, ia0 = (int)a0;
 #pragma unroll
-                for (int u8 = 0; u8 < kUR; ++u8) {
+                for (int u8 = 0; u8 < kR; ++u8) {
                     const int ar = ia0 + u8;
                     v[u8].x = (ib0 < ar) ? v[u8].x : __builtin_nan("");
                     v[u8].y = (ib0 + 1 < ar) ? v[u8].y : __builtin_nan("");
@@ -390,9 +400,9 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
             // masked entry (NaN distance) give a NaN q, which fmin drops and no comparison selects.  m0 / m1: the
             // exact minimum over the live rows of this lane's two columns (dead rows add NaN, which fmin drops).
             double lm = __builtin_inf(), m0 = __builtin_inf(), m1 = __builtin_inf();
-            double rowq[kUR];                          // this lane's smallest q per row: pass 2 looks only at rows that reach wm
+            double rowq[kR];                           // this lane's smallest q per row: pass 2 looks only at rows that reach wm
 #pragma unroll
-            for (int u8 = 0; u8 < kUR; ++u8) {
+            for (int u8 = 0; u8 < kR; ++u8) {
                 const double d0 = v[u8].x, d1 = v[u8].y;
                 const double rn = ua[u8] == ua[u8] ? 0.0 : __builtin_nan("");   // wave-uniform
                 m0 = fmin(m0, d0 + rn);
@@ -411,7 +421,7 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
                 if (wm < bq) { bq = wm; bk = ~0ull; }   // rather than kept: 128 registers less, twice the blocks per CU
                 if (a.dbg != nullptr && (it == a.dbg_it || a.dbg_it == -2) && (tid & 63) == 0) atomicAdd(&a.dbg[(a.dbg_it == -2 ? 0 : (int)blockIdx.x) * 8 + 6], 1ull);
 #pragma unroll
-                for (int u8 = 0; u8 < kUR; ++u8) {
+                for (int u8 = 0; u8 < kR; ++u8) {
                     if (__builtin_amdgcn_ballot_w64(rowq[u8] == wm) != 0ull) {      // rare; the four q are recomputed (same bits)
                         if (a.dbg != nullptr && (it == a.dbg_it || a.dbg_it == -2) && (tid & 63) == 0) atomicAdd(&a.dbg[(a.dbg_it == -2 ? 0 : (int)blockIdx.x) * 8 + 5], 1ull);
                         double d0 = v[u8].x, d1 = v[u8].y;
@@ -429,9 +439,14 @@ __global__ __launch_bounds__(kThreads) void njp_scan_kernel(NjState* h_st, const
                 }
             }
             NJP_STAMP(0, 7, false);
-            // exact minimum of this wave's sub-unit -> its bound (no cross-wave step)
+            // exact minimum of this wave's rows of the sub-unit -> this half's word of its bound (no cross-wave step, no
+            // cross-block step: a store, not a running minimum -- the bound must be able to rise)
             m = wave_fmin(m);
-            if ((tid & 63) == 0) a.umin[((int64_t)cb * G16 + g_s) * 4 + wv] = enc_f64(m);
+            if ((tid & 63) == 0) {
+                unsigned long long* um = a.umin + (((int64_t)cb * G16 + g_s) * 4 + wv) * 2;
+                if (kH == 1) *reinterpret_cast<ulonglong2*>(um) = make_ulonglong2(enc_f64(m), enc_f64(__builtin_inf()));
+                else um[uh] = enc_f64(m);
+            }
         }
         // wave winner: the smallest key among the lanes' candidates at bq, then that lane's positions and distance
         {
@@ -542,16 +557,23 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
     // records, the others a unit record (every sstride-th when all of them are defined)
     const int nseed_rows = a.nrb < kThreads / 2 ? a.nrb : kThreads / 2;
     const int nseed_units = kThreads - nseed_rows;
-    const int64_t sstride = a.all_defined && a.urecs >= 2 * nseed_units ? a.urecs / nseed_units : 1;
+    // (a.halves records per list entry: a seed thread loads all of its entry's in this round trip and keeps the one with the
+    //  smaller q -- the same threads cover the same entries as with one record each)
+    const int nent = a.urecs / a.halves;
+    const int64_t sstride = a.all_defined && nent >= 2 * nseed_units ? nent / nseed_units : 1;
     const bool seed_is_unit = tid < nseed_units;
-    NjRecord cand = r0;
+    const int64_t seed_rec = (int64_t)tid * sstride * a.halves;      // first record of this thread's entry
+    NjRecord cand = r0, cand2 = r0;
     if (test_block) {
         if (!seed_is_unit) cand = h_partials[a.urecs + (tid - nseed_units)];
-        else if ((int64_t)tid * sstride < a.urecs) cand = h_partials[(int64_t)tid * sstride];
+        else if (seed_rec < a.urecs) {
+            cand = h_partials[seed_rec];
+            if (a.halves == 2) cand2 = h_partials[seed_rec + 1];
+        }
     }
     const unsigned long long cl0 = h_cnt[0], cl1 = h_cnt[1], cl2 = h_cnt[2];      // all three list counters with the first round trip (not a second, dependent load)
     const int m3 = (int)(it % 3);
-    const unsigned long long cnt_raw = a.all_defined ? (unsigned long long)a.urecs : (m3 == 0 ? cl0 : m3 == 1 ? cl1 : cl2);
+    const unsigned long long cnt_raw = a.all_defined ? (unsigned long long)a.urecs : (unsigned long long)a.halves * (m3 == 0 ? cl0 : m3 == 1 ? cl1 : cl2);
     const int64_t uvalid = (int64_t)(cnt_raw < (unsigned long long)a.urecs ? cnt_raw : (unsigned long long)a.urecs);   // unit records written by SCAN(it)
     const double* __restrict__ Uc = a.U + (it & 1) * a.vstride;
     double* __restrict__ Un = a.U + ((it + 1) & 1) * a.vstride;
@@ -566,7 +588,7 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
     // positions rbase + 512 c + 2 t, + 1) -- one lane per group with 16 consecutive values each would touch 64 lines per
     // wave instruction and push 8 x the bytes through L1.  The block walks nsb <= kNS strips with these rows; what a
     // strip needs (its columns' row sums, rows x / y over its columns, the bounds of its units) is loaded up front.
-    struct ColData { v2d ucol, dxc, dyc, rzc; ulonglong2 um0, um1; };
+    struct ColData { v2d ucol, dxc, dyc, rzc; ulonglong2 um[4]; };      // um[w]: the two half-words of sub-unit w's bound
     int cb0 = 0, nsb = 0;
     int64_t g = 0, rbase = 0;
     bool have_g = false;
@@ -576,15 +598,17 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
 #pragma unroll
     for (int k = 0; k < kNS; ++k) {
         cd[k].ucol.x = 0.0; cd[k].ucol.y = 0.0; cd[k].dxc = cd[k].ucol; cd[k].dyc = cd[k].ucol; cd[k].rzc = cd[k].ucol;
-        cd[k].um0 = make_ulonglong2(0ull, 0ull); cd[k].um1 = cd[k].um0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) cd[k].um[w] = make_ulonglong2(0ull, 0ull);
     }
     // hop-1 part of a strip: nothing here depends on the winner
     auto load_a = [&](int cb, ColData& c) {
         const int64_t pc0 = (int64_t)cb * kTileCols + 2 * tid;                      // this thread's two strip columns (< P + 512)
         c.ucol = *reinterpret_cast<const v2d*>(Uc + pc0);
         if (have_g && g >= 32 * (int64_t)cb) {
-            const unsigned long long* up = a.umin + ((int64_t)cb * G16 + g) * 4;
-            c.um0 = *reinterpret_cast<const ulonglong2*>(up); c.um1 = *reinterpret_cast<const ulonglong2*>(up + 2);
+            const ulonglong2* up = reinterpret_cast<const ulonglong2*>(a.umin + ((int64_t)cb * G16 + g) * 8);
+#pragma unroll
+            for (int w = 0; w < 4; ++w) c.um[w] = up[w];
         }
     };
     if (test_block) {
@@ -774,7 +798,8 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
         if (k < nsb) load_b(cb0 + k, cd[k]);
     // seed candidate re-evaluated with the row sums after this merge
     double qc = PINF;
-    if (seed_is_unit && (int64_t)tid * sstride >= uvalid) cand.key = ~0ull;          // not written by this iteration's scan
+    if (seed_is_unit && seed_rec >= uvalid) { cand.key = ~0ull; cand2.key = ~0ull; }   // not written by this iteration's scan (uvalid is a multiple of a.halves)
+    if (cand2.key != ~0ull && (cand.key == ~0ull || cand2.q < cand.q)) cand = cand2;
     if (cand.key != ~0ull) {
         const int64_t ci = (int64_t)(cand.pad & 0xffffffffull), cj = (int64_t)(cand.pad >> 32);
         // the record carries D of the pair; the entry is unchanged by this merge unless one end is x or y
@@ -821,9 +846,12 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
         const int64_t pc0 = (int64_t)cb * kTileCols + 2 * tid;
         const bool pz_strip = fold && pz / kTileCols == cb;                      // block-uniform
         const bool have = have_g && g >= 32 * (int64_t)cb;
-        unsigned long long* up4 = a.umin + ((int64_t)cb * G16 + (have ? g : 0)) * 4;
-        double u4[4] = { PINF, PINF, PINF, PINF };
-        if (have) { u4[0] = dec_f64(cur.um0.x); u4[1] = dec_f64(cur.um0.y); u4[2] = dec_f64(cur.um1.x); u4[3] = dec_f64(cur.um1.y); }
+        ulonglong2* up4 = reinterpret_cast<ulonglong2*>(a.umin + ((int64_t)cb * G16 + (have ? g : 0)) * 8);
+        double u4[4] = { PINF, PINF, PINF, PINF };      // a sub-unit's bound: the smaller of its two half-words (the encoding keeps the order)
+        if (have) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) u4[w] = dec_f64(cur.um[w].x < cur.um[w].y ? cur.um[w].x : cur.um[w].y);
+        }
         // column maximum of each sub-strip (wave w holds columns 128w .. 128w+127 of the strip); minimum of the row of the
         // node leaving quarantine over the sub-strip's live columns
         double cm_part = NINF, colmin = PINF;
@@ -877,9 +905,9 @@ __global__ __launch_bounds__(kThreads, (kNS > 1 ? DPR_NJP_BIG_WAVES : 1)) void n
                 const double cmw = scm2[par][w];
                 double nm = (gz_here && g == gz) ? snew2[par][w] : PINF;      // the unit (this strip, group of pz)
                 if (pz_strip && w == wpz) nm = fmin(nm, newminA);
-                if (nm < u4[w]) {                          // persist the lowered bound (this lane is the unit's only writer here)
+                if (nm < u4[w]) {                          // persist the lowered bound, in BOTH half-words (this lane is the unit's only writer here)
                     u4[w] = nm;
-                    up4[w] = enc_f64(nm);
+                    up4[w] = make_ulonglong2(enc_f64(nm), enc_f64(nm));
                 }
                 const double lb = fmin((u4[w] - rmax) - cmw, (u4[w] - cmw) - rmax);
                 if ((cmw > NINF) && (lb <= bound)) submask |= 1 << w;
@@ -1005,9 +1033,11 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
     // T: the seed candidate of this thread (as in njp_post_kernel)
     const int nseed_rows = a.nrb < kThreads / 2 ? a.nrb : kThreads / 2;
     const int nseed_units = kThreads - nseed_rows;
-    const int64_t sstride = a.all_defined && a.urecs >= 2 * nseed_units ? a.urecs / nseed_units : 1;
+    const int nent = a.urecs / a.halves;                             // (a.halves records per list entry, see njp_post_kernel)
+    const int64_t sstride = a.all_defined && nent >= 2 * nseed_units ? nent / nseed_units : 1;
     const bool seed_is_unit = tid < nseed_units;
-    NjRecord cand = r0;
+    const int64_t seed_rec = (int64_t)tid * sstride * a.halves;
+    NjRecord cand = r0, cand2 = r0;
     int cb0 = 0;
     int64_t g0 = 0;
     // UM: the block's two chunks of 256 reference slots (the chunk sums stay per 256 slots: the canonical order of U[x]) and
@@ -1020,7 +1050,10 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
     int2 sl = make_int2(-1, -1);                             // reference slots of the two positions (-1: dead / padding)
     if (trole) {
         if (!seed_is_unit) cand = h_partials[a.urecs + (tid - nseed_units)];
-        else if ((int64_t)tid * sstride < a.urecs) cand = h_partials[(int64_t)tid * sstride];
+        else if (seed_rec < a.urecs) {
+            cand = h_partials[seed_rec];
+            if (a.halves == 2) cand2 = h_partials[seed_rec + 1];
+        }
         cb0 = h_blk_cb[tb];
         g0 = (int64_t)h_blk_g0[tb];
     } else {
@@ -1033,7 +1066,7 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
     double* __restrict__ Un = a.U + ((it + 1) & 1) * a.vstride;
     const unsigned long long cl0 = h_cnt[0], cl1 = h_cnt[1], cl2 = h_cnt[2];      // all three list counters with the first round trip (not a second, dependent load)
     const int m3 = (int)(it % 3);
-    const unsigned long long cnt_raw = a.all_defined ? (unsigned long long)a.urecs : (m3 == 0 ? cl0 : m3 == 1 ? cl1 : cl2);
+    const unsigned long long cnt_raw = a.all_defined ? (unsigned long long)a.urecs : (unsigned long long)a.halves * (m3 == 0 ? cl0 : m3 == 1 ? cl1 : cl2);
     const int64_t uvalid = (int64_t)(cnt_raw < (unsigned long long)a.urecs ? cnt_raw : (unsigned long long)a.urecs);
     const double emin = dec_f64(hdr->min_enc), eabs = dec_f64(hdr->maxabs_enc);
     v2d uc; uc.x = 0.0; uc.y = 0.0;
@@ -1048,7 +1081,8 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
         const int64_t send = njp_strips_of_rows(g0, kTG, P);
         nsb = (int)(send - cb0 < kNS ? send - cb0 : kNS);
         if (pz >= 0) uz = Uc[pz];
-        if (seed_is_unit && (int64_t)tid * sstride >= uvalid) cand.key = ~0ull;          // not written by this iteration's scan
+        if (seed_is_unit && seed_rec >= uvalid) { cand.key = ~0ull; cand2.key = ~0ull; }   // not written by this iteration's scan
+        if (cand2.key != ~0ull && (cand.key == ~0ull || cand2.q < cand.q)) cand = cand2;
         if (cand.key != ~0ull) {
             ci = (int64_t)(cand.pad & 0xffffffffull); cj = (int64_t)(cand.pad >> 32);
             if (!(ci < P && cj < P)) ci = -1;
@@ -1262,13 +1296,17 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
     }
     // small shape (one strip per block): the unit bounds travel with this round trip -- waiting for the coarse decision first
     // is a dependent round trip, and a block holds 8 KB of them
+    // um0 / um1: per strip the four sub-unit bounds, each the smaller of its two half-words (the encoding keeps the order)
     ulonglong2 um0[kNS], um1[kNS];
+    auto load_um = [&](int k) {
+        const ulonglong2* up = reinterpret_cast<const ulonglong2*>(a.umin + ((int64_t)(cb0 + k) * G16 + g) * 8);
+        const ulonglong2 p0 = up[0], p1 = up[1], p2 = up[2], p3 = up[3];
+        um0[k] = make_ulonglong2(p0.x < p0.y ? p0.x : p0.y, p1.x < p1.y ? p1.x : p1.y);
+        um1[k] = make_ulonglong2(p2.x < p2.y ? p2.x : p2.y, p3.x < p3.y ? p3.x : p3.y);
+    };
 #pragma unroll
     for (int k = 0; k < kNS; ++k) { um0[k] = make_ulonglong2(0ull, 0ull); um1[k] = um0[k]; }
-    if (kNS == 1 && nsb > 0 && have_g && g >= 32 * (int64_t)cb0) {
-        const unsigned long long* up = a.umin + ((int64_t)cb0 * G16 + g) * 4;
-        um0[0] = *reinterpret_cast<const ulonglong2*>(up); um1[0] = *reinterpret_cast<const ulonglong2*>(up + 2);
-    }
+    if (kNS == 1 && nsb > 0 && have_g && g >= 32 * (int64_t)cb0) load_um(0);
     qc = wave_fmin(qc);
     if (lane == 0) sseed[tid >> 6] = qc;
     NJP_STAMP(1, 3, true);
@@ -1321,10 +1359,7 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
     if (kNS > 1) {
 #pragma unroll
         for (int k = 0; k < kNS; ++k) {
-            if (k < nsb && have_g && g >= 32 * (int64_t)(cb0 + k)) {
-                const unsigned long long* up = a.umin + ((int64_t)(cb0 + k) * G16 + g) * 4;
-                um0[k] = *reinterpret_cast<const ulonglong2*>(up); um1[k] = *reinterpret_cast<const ulonglong2*>(up + 2);
-            }
+            if (k < nsb && have_g && g >= 32 * (int64_t)(cb0 + k)) load_um(k);
         }
     }
     NJP_STAMP(1, 5, true);
@@ -1344,7 +1379,7 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
         const int cb = cb0 + sidx;
         const bool pz_strip = fold && cbz == cb;                                 // block-uniform
         const bool have = have_g && g >= 32 * (int64_t)cb;
-        unsigned long long* up4 = a.umin + ((int64_t)cb * G16 + (have ? g : 0)) * 4;
+        ulonglong2* up4 = reinterpret_cast<ulonglong2*>(a.umin + ((int64_t)cb * G16 + (have ? g : 0)) * 8);
         double u4[4] = { PINF, PINF, PINF, PINF };
         if (have) { u4[0] = dec_f64(um0[sidx].x); u4[1] = dec_f64(um0[sidx].y); u4[2] = dec_f64(um1[sidx].x); u4[3] = dec_f64(um1[sidx].y); }
         const double newminA = (pz_strip && have_g) ? a.t2_rowmin[par * GS + g] : PINF;
@@ -1355,9 +1390,9 @@ __global__ __launch_bounds__(kThreads) void njp_post2_kernel(NjState* h_st, cons
                 const double cmw = cm4[sidx][w];
                 double nm = (gz_here && g == gz) ? s_colmin[4 * sidx + w] : PINF;      // the unit (this strip, group of pz)
                 if (pz_strip && w == wpz) nm = fmin(nm, newminA);
-                if (nm < u4[w]) {                          // persist the lowered bound (this lane is the unit's only writer here)
+                if (nm < u4[w]) {                          // persist the lowered bound, in BOTH half-words (this lane is the unit's only writer here)
                     u4[w] = nm;
-                    up4[w] = enc_f64(nm);
+                    up4[w] = make_ulonglong2(enc_f64(nm), enc_f64(nm));
                 }
                 mymin = fmin(mymin, u4[w]);
                 const double lb = fmin((u4[w] - rmax) - cmw, (u4[w] - cmw) - rmax);
@@ -1417,8 +1452,8 @@ static unsigned long long* g_njp_dbg_last = nullptr;
 // of the launchers, so that the ISA of a change to the host code can be compared with its parent's line by line.  It has no
 // other role: delete it when no such comparison is wanted (the kernels then follow the launchers' order, nothing else changes).
 [[maybe_unused]] static const void* const kNjpInstantiations[] = {
-    (const void*)njp_scan_kernel<false>, (const void*)njp_post2_kernel<kBigNS>, (const void*)njp_post_kernel<64, 1, false>, (const void*)njp_post_kernel<256, kBigNS, false>,
-    (const void*)njp_scan_kernel<true>, (const void*)njp_post_kernel<64, 1, true>, (const void*)njp_finish_kernel<true>, (const void*)njp_finish_kernel<false> };
+    (const void*)njp_scan_kernel<false, 2>, (const void*)njp_post2_kernel<kBigNS>, (const void*)njp_post_kernel<64, 1, false>, (const void*)njp_post_kernel<256, kBigNS, false>,
+    (const void*)njp_scan_kernel<true, 1>, (const void*)njp_post_kernel<64, 1, true>, (const void*)njp_finish_kernel<true>, (const void*)njp_finish_kernel<false> };
 
 // the first scan of an epoch: every unit of the rank's test blocks
 int njp_launch_list_all(const NjpArgs& a, hipStream_t s)
@@ -1427,12 +1462,13 @@ int njp_launch_list_all(const NjpArgs& a, hipStream_t s)
     DPR_HIP(hipGetLastError());
     return DPR_OK;
 }
-// SCAN: the rank's unit-scan blocks and, with a.do_rows, the new-row blocks behind them
+// SCAN: with a.do_rows the new-row blocks, then the rank's unit-scan blocks: a.halves for each of the a.ugrid entries of a pass
 int njp_launch_scan(const NjpArgs& a, hipStream_t s)
 {
     const int nrl = a.do_rows ? a.nrb : 0;
-    auto* kernel = a.rs_world > 0 ? njp_scan_kernel<true> : njp_scan_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(a.ugrid + nrl)), dim3(kThreads), 0, s, a.st, (const int32_t*)a.list, (const unsigned long long*)a.cnt,
+    auto* kernel = a.rs_world > 0 ? njp_scan_kernel<true, 1> : njp_scan_kernel<false, 2>;
+    if (a.halves != (a.rs_world > 0 ? 1 : 2)) { set_error("njp_launch_scan: record layout does not match the kernel"); return DPR_ERR_STATE; }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(a.halves * a.ugrid + nrl)), dim3(kThreads), 0, s, a.st, (const int32_t*)a.list, (const unsigned long long*)a.cnt,
                        (const double*)a.xpart, nrl, a);
     DPR_HIP(hipGetLastError());
     return DPR_OK;
@@ -1533,7 +1569,7 @@ static int njp_carve(NjPruned* qp, char* slab, int64_t P, int64_t N, int local_r
     take(q.slot_of_pos, vec, 0xff);      // -1: dead / padding
     take(q.pos_of_slot, vec, 0xff);      // -1: slot not alive
     take(q.perm, vec);
-    q.nunits_alloc = S * G16 * 4;        // four sub-strip bounds per unit
+    q.nunits_alloc = S * G16 * 8;        // four sub-strip bounds per unit, one word per row half of the scan each
     take(q.umin, (size_t)q.nunits_alloc);
     // unit-sharded mode: one list and one counter quadruple per rank held here (all of them for virtual ranks)
     q.list_stride = unit_total(P) + kScanBlocks + 64;
@@ -1881,7 +1917,9 @@ void njp_free(NjPruned& q)
     q = NjPruned();
 }
 
-// unit-sharded mode: unit-scan blocks per rank and unit records in total
+// unit-sharded mode: list entries per pass of a rank's scan and of all ranks'; every entry is scanned by kNjpHalves blocks, one
+// unit record each
+constexpr int kNjpHalves = 2;
 static int njp_grid_rank(const NjPruned& q) { return q.sh_world > 1 ? (q.scan_grid / q.sh_world > 0 ? q.scan_grid / q.sh_world : 1) : q.scan_grid; }
 static int njp_grid_total(const NjPruned& q) { return q.sh_world > 1 ? njp_grid_rank(q) * q.sh_world : q.scan_grid; }
 // the ranks this process launches for: [first, last)
@@ -1906,9 +1944,10 @@ static NjpArgs njp_args(NjBuffers& b, int v)
     a.list = q.list + (int64_t)slot * q.list_stride;
     a.cnt = sh ? q.cnt_all + 4 * slot : b.st->cnt_list;
     a.ugrid = njp_grid_rank(q);
-    a.urecs = njp_grid_total(q);
+    a.halves = kNjpHalves;
+    a.urecs = kNjpHalves * njp_grid_total(q);
     a.nrb = (int)((q.P + kTileCols - 1) / kTileCols);
-    a.rec_off = sh ? v * a.ugrid : 0;
+    a.rec_off = sh ? v * kNjpHalves * a.ugrid : 0;
     a.all_defined = sh ? 1 : 0;
     a.sh_rank = sh ? v : 0; a.sh_world = sh ? q.sh_world : 1;
     a.cnt_all = sh ? q.cnt_all : nullptr;
@@ -1949,7 +1988,7 @@ static int njp_enqueue_iteration(NjBuffers& b, hipStream_t s, bool sample = fals
     }
     if (!q.sh_virtual) {
         if (!q.gather) { set_error("njp: unit-sharded mode without a gather callback"); return DPR_ERR_STATE; }
-        if (int rc = q.gather(q.gather_ctx, b.partials, sizeof(NjRecord) * (size_t)njp_grid_rank(q), s)) return rc;
+        if (int rc = q.gather(q.gather_ctx, b.partials, sizeof(NjRecord) * (size_t)(kNjpHalves * njp_grid_rank(q)), s)) return rc;
     }
     // (virtual ranks: the update runs once, with the first rank's tests; the other ranks' tests follow in launches of
     // their own -- they read only what the update leaves alone: the current U buffer, rows x and y, the scan records)

@@ -51,8 +51,9 @@ struct NjpArgs {
     int tg, ns;                                                  // ... of tg row groups x up to ns strips
     int nupd;                                                    // update blocks of this post launch
     int32_t* list; unsigned long long* cnt;     // the list of THIS launch's rank and its counters cnt[0..2]
-    int ugrid;        // unit-scan blocks per rank
-    int urecs;        // unit records in partials (ugrid x ranks); the new-row records follow them
+    int ugrid;        // list entries per pass of this rank's unit scan (halves x ugrid unit blocks)
+    int halves;       // row halves per unit = blocks and records per list entry: 2 (single GPU, unit-sharded), 1 (row-sharded)
+    int urecs;        // unit records in partials (halves x ugrid x ranks); the new-row records follow them
     int nrb;          // new-row blocks = ceil(P / 512)
     int rec_off;      // first unit record of this launch's rank
     int all_defined;  // unit-sharded mode: every unit record is written by every scan

@@ -266,6 +266,7 @@ static NjpArgs njr_args(NjBuffers& b)
     a.tg = kNjrChunk / kUR; a.ns = 1; a.nupd = 0;
     a.list = q.list; a.cnt = b.st->cnt_list;
     a.ugrid = q.scan_grid / r.world > 0 ? q.scan_grid / r.world : 1;
+    a.halves = 1;                                  // (one block per unit: the second word of every sub-unit bound holds +inf)
     a.urecs = (a.ugrid + 1) * r.world;
     a.nrb = (int)((q.P + kTileCols - 1) / kTileCols);
     a.rec_off = r.rank * (a.ugrid + 1) + 1;
