@@ -153,6 +153,9 @@ def load_library():
     L.dpr_msa_resample.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
     L.dpr_get_msa_boot_weights.argtypes = [C.c_void_p, c_i32p]
     L.dpr_msa_boot_weights.argtypes = [C.c_uint64, C.c_int64, C.c_int64, c_i32p]
+    L.dpr_get_msa_site_coverage.argtypes = [C.c_void_p, c_i32p]
+    L.dpr_msa_filter_sites.argtypes = [C.c_void_p, C.c_int]
+    L.dpr_msa_filter_sites.restype = C.c_int64
     L.dpr_split_support.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]
     L.dpr_comm_sum_i32.argtypes = [C.c_void_p, c_i32p, C.c_int64]
     L.dpr_transfer_support.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
@@ -615,12 +618,14 @@ class Dipper:
     def set_msa(self, packed4, L):
         p = np.ascontiguousarray(packed4, dtype=np.uint64)
         _chk(self.L, self.L.dpr_set_msa(self.h, _p(p, c_u64p), p.shape[0], L))
+        self._msa_sites = int(L)      # (msa_site_coverage sizes its result by it)
 
     def set_msa_aa(self, codes):
         """protein alignment: codes [n][L] uint8 as pack_aa_many builds them (>= 20: not a residue); source stays SRC_MSA"""
         p = np.ascontiguousarray(codes, dtype=np.uint8)
         assert p.ndim == 2
         _chk(self.L, self.L.dpr_set_msa_aa(self.h, _p(p, C.POINTER(C.c_uint8)), p.shape[0], p.shape[1]))
+        self._msa_sites = int(p.shape[1])
 
     def set_matrix_lower(self, rows, n):
         r = np.ascontiguousarray(rows, dtype=np.float64)
@@ -944,6 +949,20 @@ class Dipper:
         out = np.zeros(L, dtype=np.int32)
         _chk(self.L, self.L.dpr_get_msa_boot_weights(self.h, _p(out, c_i32p)))
         return out
+
+    def msa_site_coverage(self):
+        """cov[c]: the sequences of the current alignment that hold a symbol at column c (one entry per site)"""
+        sites = getattr(self, "_msa_sites", 0)
+        if not sites:
+            raise DipperError(-3, "msa_site_coverage: call set_msa or set_msa_aa first")
+        out = np.zeros(sites, dtype=np.int32)
+        _chk(self.L, self.L.dpr_get_msa_site_coverage(self.h, _p(out, c_i32p)))
+        return out
+
+    def msa_filter_sites(self, permille):
+        """keeps the columns with 1000 cov >= permille n (1000: complete deletion), on the device; returns the sites kept"""
+        self._msa_sites = int(_chk(self.L, self.L.dpr_msa_filter_sites(self.h, permille)))
+        return self._msa_sites
 
     def comm_sum_i32(self, values):
         """in-place integer sum over the context's ranks"""

@@ -420,6 +420,9 @@ constexpr int kMsaBand = 15;
 int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hipStream_t s);
 void msa_free(MsaBuffers& m);
 int msa_restage(MsaBuffers& m, hipStream_t s);     // m.xstage of the active planes again (nothing to do without xstage)
+// everything that follows from the planes alone (jc_tab, xstage): allocated for m.n / m.L, then filled from m.planes
+int msa_derived_alloc(MsaBuffers& m);
+int msa_derive(MsaBuffers& m, hipStream_t s);
 // mash_index.hip: out[i] = in[0] + ... + in[i] (in and out must not alias); synchronises s
 int mi_inclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s);
 int msa_dist_rows(const MsaBuffers& m, NjBuffers& b, int dist_type, hipStream_t s);
@@ -569,6 +572,8 @@ struct TileOut {
 };
 // msa_aa.hip: the protein alphabet behind the same entry points (msa.hip dispatches on MsaBuffers::aa)
 int msa_aa_upload(MsaBuffers& m, const uint8_t* codes, int64_t n, int64_t L, hipStream_t s);
+int msa_aa_derived_alloc(MsaBuffers& m);      // xstage, aa_nx
+int msa_aa_derive(MsaBuffers& m, hipStream_t s);
 int msa_aa_launch(int dist_type, hipStream_t s, const MsaBuffers& m, double* D, int64_t ld, int64_t rows, int rank, int world,
                   int64_t row0, int64_t col0, int64_t ncols, int transposed);
 int msa_aa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32_t* d_match, hipStream_t s);

@@ -785,6 +785,40 @@ __global__ __launch_bounds__(kThreads) void msa_counts_row_kernel(const uint32_t
     match[c] = m;
 }
 
+// What an alignment's planes alone decide, for nucleotides: jc_tab (the full table up to kMsaTabSites sites, the band above, none
+// under DPR_MSA_NO_BAND or from 2^30 sites) and xstage (none under DPR_MSA_NO_FAST).  msa_derived_alloc allocates them for
+// m.n / m.L (both must be null), msa_derive fills them from m.planes.  msa_upload and the site filter (sites.hip) share the two.
+int msa_derived_alloc(MsaBuffers& m)
+{
+    const int64_t L = m.L;
+    int64_t cells = 0;
+    if (L <= kMsaTabSites) cells = (L + 1) * (L + 1);
+    else if (L < (1 << 30) && !std::getenv("DPR_MSA_NO_BAND")) cells = (L + 1) * (kMsaBand + 1);
+    if (cells) DPR_HIP(hipMalloc(&m.jc_tab, sizeof(double) * (size_t)(2 * cells)));
+    if (!std::getenv("DPR_MSA_NO_FAST"))      // (the switch exists for the A/B runs of profiles/msa_block_bench.py and for the tests)
+        DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)m.n));
+    return DPR_OK;
+}
+
+int msa_derive(MsaBuffers& m, hipStream_t s)
+{
+    const int64_t n = m.n, L = m.L;
+    if (m.jc_tab && L <= kMsaTabSites) {
+        const int64_t cells = (L + 1) * (L + 1);
+        hipLaunchKernelGGL(msa_jc_table_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
+        DPR_HIP(hipGetLastError());
+    } else if (m.jc_tab) {
+        const int64_t cells = (L + 1) * (kMsaBand + 1);
+        hipLaunchKernelGGL(msa_jc_band_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
+        DPR_HIP(hipGetLastError());
+    }
+    if (m.xstage) {
+        hipLaunchKernelGGL(msa_xstage_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, n, m.W32, L, m.xstage);
+        DPR_HIP(hipGetLastError());
+    }
+    return DPR_OK;
+}
+
 // The packed array goes to a temporary device buffer in one hipMemcpyAsync and msa_planes_kernel converts it.  Measured against
 // reading the caller's registered array from the kernel and against a pipeline of two pinned chunks: the copy is the fastest
 // of the three at 30 000 x 10 000 and at 550 000 x 1 000 (profiles/msa_upload/variants.jsonl).
@@ -804,16 +838,11 @@ int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hip
     m.n = n; m.L = L; m.W32 = (L + 31) / 32;
     const int64_t W64 = (L + 15) / 16;
     // every buffer first: no hipMalloc between the launches below
-    int64_t cells = 0;
-    if (L <= kMsaTabSites) cells = (L + 1) * (L + 1);
-    else if (L < (1 << 30) && !std::getenv("DPR_MSA_NO_BAND")) cells = (L + 1) * (kMsaBand + 1);
     DevBuf<uint64_t> d_in;
     DPR_HIP(d_in.alloc((size_t)(n * W64)));
     lap("d_in allocated");
     DPR_HIP(hipMalloc(&m.planes, sizeof(uint32_t) * (size_t)(4 * n * m.W32)));
-    if (cells) DPR_HIP(hipMalloc(&m.jc_tab, sizeof(double) * (size_t)(2 * cells)));
-    if (!std::getenv("DPR_MSA_NO_FAST"))      // (the switch exists for the A/B runs of profiles/msa_block_bench.py and for the tests)
-        DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)n));
+    if (int rc = msa_derived_alloc(m)) return rc;
     lap("planes, table, xstage allocated (3 hipMalloc)");
     DPR_HIP(hipMemcpyAsync(d_in, packed4, sizeof(uint64_t) * (size_t)(n * W64), hipMemcpyHostToDevice, s));
     lap("H2D copy");
@@ -823,17 +852,7 @@ int msa_upload(MsaBuffers& m, const uint64_t* packed4, int64_t n, int64_t L, hip
                        m.W32, m.planes);
     DPR_HIP(hipGetLastError());
     lap("planes kernel");
-    if (L <= kMsaTabSites) {
-        hipLaunchKernelGGL(msa_jc_table_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
-        DPR_HIP(hipGetLastError());
-    } else if (cells) {
-        hipLaunchKernelGGL(msa_jc_band_kernel, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (int)L, m.jc_tab);
-        DPR_HIP(hipGetLastError());
-    }
-    if (m.xstage) {
-        hipLaunchKernelGGL(msa_xstage_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, n, m.W32, L, m.xstage);
-        DPR_HIP(hipGetLastError());
-    }
+    if (int rc = msa_derive(m, s)) return rc;
     lap("table and xstage kernels");
     DPR_HIP(hipStreamSynchronize(s));      // (d_in is read until here)
     lap("final sync");

@@ -287,6 +287,23 @@ int msa_aa_counts_row(const MsaBuffers& m, int64_t row, int32_t* d_useful, int32
     return DPR_OK;
 }
 
+// what a protein alignment's planes alone decide: xstage and aa_nx.  msa_aa_derived_alloc allocates them for m.n (both must be
+// null), msa_aa_derive fills them from m.planes; msa_aa_upload and the site filter (sites.hip) share the two
+int msa_aa_derived_alloc(MsaBuffers& m)
+{
+    DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)m.n));
+    DPR_HIP(hipMalloc(&m.aa_nx, sizeof(int32_t) * (size_t)m.n));
+    return DPR_OK;
+}
+
+int msa_aa_derive(MsaBuffers& m, hipStream_t s)
+{
+    hipLaunchKernelGGL(msa_aa_xstage_kernel, dim3((unsigned)((m.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, m.n, m.W32,
+                       m.xstage, m.aa_nx);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
 int msa_aa_upload(MsaBuffers& m, const uint8_t* codes, int64_t n, int64_t L, hipStream_t s)
 {
     msa_free(m);
@@ -295,15 +312,12 @@ int msa_aa_upload(MsaBuffers& m, const uint8_t* codes, int64_t n, int64_t L, hip
     DPR_HIP(d_in.alloc((size_t)(n * L)));
     DPR_HIP(hipMemcpyAsync(d_in, codes, (size_t)(n * L), hipMemcpyHostToDevice, s));
     DPR_HIP(hipMalloc(&m.planes, sizeof(uint32_t) * (size_t)(kAaPlanes * n * m.W32)));
-    DPR_HIP(hipMalloc(&m.xstage, sizeof(unsigned long long) * (size_t)n));
-    DPR_HIP(hipMalloc(&m.aa_nx, sizeof(int32_t) * (size_t)n));
+    if (int rc = msa_aa_derived_alloc(m)) return rc;
     const int64_t total = n * m.W32;
     const unsigned grid = (unsigned)((total + kThreads - 1) / kThreads > 8192 ? 8192 : (total + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(msa_aa_planes_kernel, dim3(grid ? grid : 1), dim3(kThreads), 0, s, (const uint8_t*)d_in, n, L, m.W32, m.planes);
     DPR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(msa_aa_xstage_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (const uint32_t*)m.planes, n, m.W32,
-                       m.xstage, m.aa_nx);
-    DPR_HIP(hipGetLastError());
+    if (int rc = msa_aa_derive(m, s)) return rc;
     DPR_HIP(hipStreamSynchronize(s));      // (d_in is read until here)
     return DPR_OK;
 }

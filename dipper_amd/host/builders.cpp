@@ -11,6 +11,8 @@
 #include <mutex>
 #include <thread>
 
+#include <sys/stat.h>
+
 namespace dipper {
 
 bool& bionjOption()
@@ -23,6 +25,59 @@ int& upgmaOption()
 {
     static int linkage = -1;
     return linkage;
+}
+
+SiteFilterOption& siteFilterOption()
+{
+    static SiteFilterOption o;
+    return o;
+}
+
+int parseSiteCoverage(const std::string& v)
+{
+    // per mille from the text, as --bootstrap-taxa-cutoff: digits, at most one point, at most three places; the integer part is
+    // zeros (or empty) with any places, or a one with places that are all zero
+    const size_t dot = v.find('.');
+    const std::string ip = v.substr(0, dot), fp = dot == std::string::npos ? "" : v.substr(dot + 1);
+    if (v.empty() || (ip.empty() && fp.empty()) || fp.size() > 3 || ip.size() > 20) return 0;
+    for (char ch : ip) if (!std::isdigit((unsigned char)ch)) return 0;
+    for (char ch : fp) if (!std::isdigit((unsigned char)ch)) return 0;
+    int pm = 0;
+    for (size_t i = 0; i < 3; ++i) pm = 10 * pm + (i < fp.size() ? fp[i] - '0' : 0);
+    size_t ones = 0, others = 0;
+    for (size_t i = 0; i < ip.size(); ++i) {
+        if (ip[i] == '1' && i + 1 == ip.size()) ++ones;
+        else if (ip[i] != '0') ++others;
+    }
+    if (others) return 0;
+    if (ones) return pm == 0 ? 1000 : 0;
+    return pm;      // (0: out of range)
+}
+
+std::string siteCoverageText(int permille)
+{
+    if (permille >= 1000) return "1";
+    char buf[16];
+    std::snprintf(buf, sizeof(buf), "0.%03d", permille);
+    std::string t = buf;
+    while (t.back() == '0') t.pop_back();
+    return t;
+}
+
+void filterSites(dpr_ctx* ctx, int64_t n, int64_t L, bool report)
+{
+    SiteFilterOption& o = siteFilterOption();
+    if (!o.permille) return;
+    const int64_t kept = dpr_msa_filter_sites(ctx, o.permille);
+    if (kept < 0) {
+        const std::string why = dpr_last_error();
+        struct stat st;
+        if (rankInfo().rank == 0 && !o.outputFile.empty() && stat(o.outputFile.c_str(), &st) == 0 && S_ISREG(st.st_mode))
+            std::remove(o.outputFile.c_str());
+        die("ERROR: --site-coverage " + o.text + ": " + why);
+    }
+    o.kept = kept;
+    if (report) std::cerr << "Sites: kept " << kept << " of " << L << " (coverage >= " << o.text << " of " << n << " sequences)\n";
 }
 
 DeviceContext::DeviceContext(int device)
@@ -142,8 +197,9 @@ void MSADeviceArrays::allocateDeviceArrays(DeviceContext& dev, const PackedSeque
     numSequences = packed.numSequences;
     if (numSequences < 2) die("ERROR: need at least two sequences");
     seqLen = packed.seqLen;
-    if (uploaded) return;      // (AsyncDeviceContext::uploadMSA did it on the device thread)
-    gpuCheck(dpr_set_msa(dev.ctx, packed.flat.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa");
+    // (uploaded: AsyncDeviceContext::uploadMSA did it on the device thread)
+    if (!uploaded) gpuCheck(dpr_set_msa(dev.ctx, packed.flat.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa");
+    filterSites(dev.ctx, (int64_t)numSequences, (int64_t)seqLen, true);
 }
 
 void MashDeviceArrays::allocateDeviceArrays(DeviceContext& dev, const PackedSequences& packed)
@@ -196,6 +252,7 @@ void MSADeviceArrays::allocateDeviceArrays(DeviceContext& dev, const std::vector
     std::vector<uint64_t> flat;
     packAligned(seqs, ids, flat, seqLen);
     gpuCheck(dpr_set_msa(dev.ctx, flat.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa");
+    filterSites(dev.ctx, (int64_t)numSequences, (int64_t)seqLen, true);
 }
 
 void MSADeviceArrays::allocateDeviceArraysProtein(DeviceContext& dev, const std::vector<std::string>& seqs, const std::vector<int>& ids)
@@ -217,6 +274,7 @@ void MSADeviceArrays::allocateDeviceArraysProtein(DeviceContext& dev, const std:
         });
     for (auto& th : pool) th.join();
     gpuCheck(dpr_set_msa_aa(dev.ctx, codes.data(), (int64_t)numSequences, (int64_t)seqLen), "dpr_set_msa_aa");
+    filterSites(dev.ctx, (int64_t)numSequences, (int64_t)seqLen, true);
 }
 
 void NJDeviceArrays::getDismatrix(DeviceContext& dev, int numSequences, Param& params, MatrixReader* matrixReader)

@@ -29,6 +29,10 @@ struct Param {  // src/mash_placement.cuh:16-32
     std::string in = "r", out = "t";
     uint64_t batchSize = 0, backboneSize = 0;
     bool protein = false;      // --protein: the aligned input holds amino acids (no reference counterpart)
+    // --site-coverage / --complete-deletion (filterSites fills both in; empty = not given): the threshold as the jplace
+    // metadata names it and the sites the filter kept
+    std::string siteCoverage;
+    int64_t sitesKept = 0;
 };
 
 [[noreturn]] void die(const std::string& msg);   // prints msg to stderr, exit(1)
@@ -134,6 +138,24 @@ bool& bionjOption();
 // --upgma (0) / --wpgma (1): the linkage every tree of this command is clustered with (dpr_upgma_run in place of dpr_nj_run);
 // -1 = NJ.  Set by main() before the first tree
 int& upgmaOption();
+
+// --site-coverage X / --complete-deletion (-i m): every alignment this command uploads -- the three MSADeviceArrays uploads and the
+// bootstrap's rank-local context -- keeps only the columns in which at least X of the sequences hold a symbol
+// (dpr_msa_filter_sites).  Set by main() before the first upload.
+struct SiteFilterOption {
+    int permille = 0;            // X in per mille, 0 = off
+    std::string text;            // X in canonical form: "1", "0.5", "0.667"
+    std::string outputFile;      // -O: rank 0 removes it again when no site is kept (it is opened before the upload)
+    int64_t kept = 0;            // sites the last filter kept
+};
+SiteFilterOption& siteFilterOption();
+// Per mille of a decimal 0 < X <= 1 with at most three places ("1", "1.000", "0.5", ".25"), from the text alone (no double);
+// 0 for anything else.  siteCoverageText writes a per mille value back in canonical form.
+int parseSiteCoverage(const std::string& v);
+std::string siteCoverageText(int permille);
+// Filters the alignment of n sequences x L sites that ctx has just uploaded, when the option is on.  No site kept: the message,
+// the output file removed, exit 1.  report: the line `Sites: kept K of L (coverage >= X of N sequences)` on stderr.
+void filterSites(dpr_ctx* ctx, int64_t n, int64_t L, bool report);
 
 struct DeviceContext {  // replaces cudaSetDevice (src/tree_generation.cu:240-245)
     dpr_ctx* ctx = nullptr;

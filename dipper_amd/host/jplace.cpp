@@ -110,6 +110,10 @@ void writeJplace(std::ostream& os, const Tree& t, const std::vector<std::string>
         out.put(",\"bootstrap_replicates\":"); out.put(std::to_string(bo.replicates));
         out.put(",\"bootstrap_seed\":"); out.put(std::to_string(bo.seed));
     }
+    if (!params.siteCoverage.empty()) {
+        out.put(",\"site_coverage\":"); putJson(out, params.siteCoverage);
+        out.put(",\"sites_kept\":"); out.put(std::to_string(params.sitesKept));
+    }
     out.put("}\n}\n");
     os.write(out.s.data(), (std::streamsize)out.s.size());
 }

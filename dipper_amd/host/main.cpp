@@ -82,6 +82,19 @@ static const char* kHelp =
     "                              over the sites where both sequences hold a residue.  -d 1 (p-distance,\n"
     "                              default), 2 (JC with 20 states), 7 or 8; conventional NJ, placement,\n"
     "                              --add and -o d / -o j; not with --bootstrap or divide-and-conquer\n"
+    "  --site-coverage arg         Keep only the alignment columns in which at least arg of the sequences hold\n"
+    "                              a symbol (A, C, G, T/U; with --protein one of the 20 residues): a decimal\n"
+    "                              0 < arg <= 1 with at most three places; a column exactly at the threshold\n"
+    "                              is kept (partial deletion; without the option every pair of sequences\n"
+    "                              uses the sites it has: pairwise deletion).  The columns are counted and\n"
+    "                              removed on the GPU after the upload; everything else runs on the filtered\n"
+    "                              alignment.  -i m only; every -d, -m and -o, --protein, --bionj, --nni,\n"
+    "                              --spr, --upgma, --wpgma, --bootstrap (replicates resample the filtered\n"
+    "                              alignment), --gpus / --devices.  With --add the coverage is taken over\n"
+    "                              all sequences of the input file, backbone and queries together.  No\n"
+    "                              column kept: an error, no output file\n"
+    "  --complete-deletion         As --site-coverage 1: only the columns without any gap or ambiguity code\n"
+    "                              (complete deletion).  Not together with --site-coverage\n"
     "  --bionj                     Build the tree with BIONJ (Gascuel 1997) instead of NJ: the same pair\n"
     "                              selection and branch lengths; the distances of a new node are a\n"
     "                              variance-weighted mean of its children's.  Wherever conventional NJ\n"
@@ -138,6 +151,7 @@ static const Opt kOpts[] = {
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
     { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
+    { "site-coverage", 0, true }, { "complete-deletion", 0, false },
 };
 
 static void usageError(const std::string& what)
@@ -269,7 +283,7 @@ int main(int argc, char** argv)
     if (vm.count("dump-jplace")) {
         // developer aid (no GPU): the jplace writer on rows from a text file.  --dump-jplace FILE with --input-tree; FILE holds per
         // query a line `NAME K` and K lines `EDGE COUNT DISTAL PENDANT` (strtod: nan and inf are read as such); --bootstrap N sets
-        // the replicates.  The file goes to stdout.
+        // the replicates, --site-coverage X the threshold named in the metadata.  The file goes to stdout.
         std::ifstream tf(strOr(vm, "input-tree", ""));
         if (!tf) { std::cerr << "ERROR: Unable to open input tree file: " << strOr(vm, "input-tree", "") << "\n"; return 1; }
         std::string nwk;
@@ -297,6 +311,8 @@ int main(int argc, char** argv)
         params.distanceType = stoiOr(vm, "distance-type", 1);
         BootstrapOptions bo;
         bo.replicates = (int64_t)stoiOr(vm, "bootstrap", 0);
+        // (--site-coverage X: the two metadata fields of a filtered run, with no site counted: sites_kept 0)
+        if (vm.count("site-coverage") && parseSiteCoverage(vm["site-coverage"])) params.siteCoverage = siteCoverageText(parseSiteCoverage(vm["site-coverage"]));
         writeJplace(std::cout, t, names, rows, params, bo);
         return 0;
     }
@@ -363,6 +379,18 @@ int main(int argc, char** argv)
         if (dt != DPR_DIST_UNCORRECTED && dt != DPR_DIST_JC && dt != DPR_DIST_POISSON && dt != DPR_DIST_KIMURA) usageError("--protein takes -d 1, 2, 7 or 8");
         if (vm.count("bootstrap")) usageError("--bootstrap is not available with --protein (nucleotide alignments only)");
         if (strOr(vm, "algorithm", "0") == "3") usageError("divide-and-conquer (-m 3) is not available with --protein; use -m 1 or -m 2");
+    }
+    // --site-coverage / --complete-deletion: what the arguments alone decide, before any input is read or a GPU touched
+    if (vm.count("site-coverage") || vm.count("complete-deletion")) {
+        if (vm.count("site-coverage") && vm.count("complete-deletion"))
+            usageError("--complete-deletion is --site-coverage 1: give one of the two");
+        if (strOr(vm, "input-format", "r") != "m") usageError("--site-coverage / --complete-deletion need aligned sequences (-i m)");
+        const int pm = vm.count("complete-deletion") ? 1000 : parseSiteCoverage(vm["site-coverage"]);
+        if (pm < 1) usageError("--site-coverage: a decimal 0 < x <= 1 with at most three places (0.5)");
+        SiteFilterOption& sf = siteFilterOption();      // every alignment this command uploads is filtered (MSADeviceArrays, the bootstrap's rank-local context)
+        sf.permille = pm;
+        sf.text = siteCoverageText(pm);
+        sf.outputFile = vm["output-file"];
     }
     // -o j (placements on a fixed backbone): what the arguments alone decide, before any input is read or a GPU touched
     const bool jplace = strOr(vm, "output-format", "t") == "j";
@@ -624,6 +652,7 @@ int main(int argc, char** argv)
                     std::cerr << "Queries without a finite placement (not finite distances to the backbone), left out of the file: " << left_out
                               << " (" << some << (left_out > 5 ? ", ..." : "") << ")\n";
             }
+            if (siteFilterOption().permille) { params.siteCoverage = siteFilterOption().text; params.sitesKept = siteFilterOption().kept; }
             writeJplace(*output_, t, names, rows, params, boot);
             if (cliLog()) std::cerr << "  placements written at " << ms_since(inputStart) << " ms\n";
             printRankSummary(dev.ctx);

@@ -170,6 +170,7 @@ void bootstrapNeighbourJoiningTree(DeviceContext& dev, int numSequences, Param& 
         if (bionjOption())
             if (int rc = dpr_ctx_set_nj_variant(rctx, 1)) fail(ri.rank, "dpr_ctx_set_nj_variant (rank-local context)", rc);
         if (int rc = dpr_set_msa(rctx, packed4, n, seqLen)) fail(ri.rank, "dpr_set_msa (rank-local context)", rc);
+        filterSites(rctx, n, seqLen, false);      // (--site-coverage: the replicates resample the filtered alignment, as on one rank)
     }
     std::vector<int32_t> rx((size_t)k), ry((size_t)k);
     std::vector<double> rbx((size_t)k), rby((size_t)k);

@@ -531,6 +531,28 @@ int dpr_ctx_set_place_fixed_batch(dpr_ctx *ctx, int64_t queries);
 /* distance blocks / scan + reduce of the last dpr_place_fixed_run in milliseconds (HIP events, summed over the batches) */
 int dpr_get_place_fixed_timing(dpr_ctx *ctx, double *dist_ms, double *scan_ms);
 
+/* ---- complete and partial deletion of gappy alignment sites (no reference counterpart) -------------------------------------
+ * A sequence HOLDS A SYMBOL at column c when its not-a-base / not-a-residue plane bit is 0 there: nucleotides, one of A, C, G,
+ * T/U as dpr_pack4 codes them; protein, one of the 20 residues as dpr_pack_aa codes them.  cov[c], 0 <= c < L, is the number of
+ * the n sequences that hold a symbol at c.  With a threshold permille in 1 .. 1000 column c is KEPT iff
+ *   1000 * cov[c] >= permille * n      (64-bit integers: a tie is kept)
+ * so permille = 1000 is complete deletion, and permille = 1 drops only the columns in which no sequence holds a symbol as long
+ * as n <= 1000 (of 30 000 sequences it asks for 30).  The filtered alignment is the kept columns in ascending order; L' is
+ * their number.
+ * Equivalence: after a successful filter the context is indistinguishable, bit for bit, from a fresh one that uploaded the
+ * host-filtered alignment with dpr_set_msa / dpr_set_msa_aa -- the planes with their padding, the per-sequence stage bits and
+ * counts, the distance table (full table or band by L', not L), hence dpr_get_msa_counts, every dpr_dist_matrix /
+ * dpr_msa_dist_block type, and dpr_msa_resample(seed, r) for nucleotides, whose column draws are a function of L'.
+ * The filter is one-way: the uploaded alignment is not kept; a new dpr_set_msa / dpr_set_msa_aa replaces the filtered one. */
+/* cov[] (L entries) of the context's current alignment */
+int dpr_get_msa_site_coverage(dpr_ctx *ctx, int32_t *out);
+/* Returns L' >= 1, or DPR_ERR_ARG for a permille outside 1 .. 1000 and when no column would be kept (the alignment is then
+ * untouched and dpr_last_error names the best coverage seen), DPR_ERR_STATE without an uploaded alignment or while a bootstrap
+ * replicate is active.  L' == L rewrites nothing.  Otherwise the planes are rebuilt on the device at L' sites, the bootstrap
+ * buffers are released and everything derived from the planes is built again as the uploads build it (DPR_MSA_NO_FAST /
+ * DPR_MSA_NO_BAND apply). */
+int64_t dpr_msa_filter_sites(dpr_ctx *ctx, int permille);
+
 /* ---- bootstrap support of NJ trees from aligned sequences (no reference counterpart) ---------------------------------------
  * Replicate r (0-based) of an alignment of L sites draws L columns with replacement (uint64 arithmetic, wrapping):
  *   mix64(z) = splitmix64's finaliser; key_r = mix64(seed ^ mix64(r)); column_t = ((mix64(key_r ^ t) >> 32) * L) >> 32,
