@@ -176,6 +176,17 @@ def load_library():
     L.dpr_upgma_host.argtypes = [c_f64p, C.c_int64, C.c_int, c_i32p, c_i32p, c_f64p]
     L.dpr_get_upgma_stats.argtypes = [C.c_void_p, c_i64p]
     L.dpr_get_upgma_timing.argtypes = [C.c_void_p, c_f64p]
+    _fit_out = [c_f64p, c_f64p, c_i64p, c_i32p]
+    L.dpr_tree_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_i32p, c_f64p] + _fit_out
+    L.dpr_tree_fit_host.argtypes = [c_f64p, C.c_int64, C.c_int64, c_i32p, c_f64p] + _fit_out
+    L.dpr_tree_fit_derive.argtypes = [c_f64p]
+    L.dpr_tree_patristic_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, c_i32p, c_f64p, C.c_int64, C.c_int64, c_f64p]
+    L.dpr_tree_from_nj.argtypes = [C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p, C.c_double, c_i32p, c_f64p, c_i64p]
+    L.dpr_tree_from_kids.argtypes = [C.c_int64, c_i32p, C.c_int32, c_f64p, c_i32p, c_f64p, c_i64p]
+    L.dpr_tree_from_upgma.argtypes = [C.c_int64, c_i32p, c_i32p, c_f64p, c_i32p, c_f64p, c_i64p]
+    L.dpr_get_fit_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_get_fit_timing.argtypes = [C.c_void_p, c_f64p, c_f64p, c_f64p]
+    L.dpr_ctx_set_fit_compare.argtypes = [C.c_void_p, C.c_int]
     L.dpr_transfer_support_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p]
     L.dpr_transfer_taxa.argtypes = [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
@@ -478,6 +489,96 @@ def upgma_host(D, linkage=0):
     mx, my, h = np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.float64)
     _chk(lib, lib.dpr_upgma_host(_p(rows, c_f64p), n, int(linkage), _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p)))
     return dict(merge_x=mx[: n - 1], merge_y=my[: n - 1], height=h[: n - 1])
+
+
+FIT_SUMS = ("n", "skipped", "sum_d", "sum_p", "sum_dd", "sum_pp", "sum_dp", "ss", "wss", "n_w", "max_e", "rms", "rms_rel", "explained",
+            "cophenetic", "spare")
+
+
+def _tree_args(n, parent, length):
+    parent = np.ascontiguousarray(np.asarray(parent, dtype=np.int32).reshape(-1))
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.float64).reshape(-1))
+    assert len(parent) == len(length)
+    return parent, length, len(parent)
+
+
+def _fit_result(out):
+    sums, ss, pairs, worst = out
+    return dict(sums=sums, taxon_ss=ss, taxon_pairs=pairs, worst=worst, **{k: float(sums[i]) for i, k in enumerate(FIT_SUMS)})
+
+
+def _fit_out(n):
+    out = (np.zeros(16), np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(2, dtype=np.int32))
+    return out, (_p(out[0], c_f64p), _p(out[1], c_f64p), _p(out[2], c_i64p), _p(out[3], c_i32p))
+
+
+def tree_fit_host(D, parent, length):
+    """Fit of the tree (parent, length: m entries each, tips 0 .. n-1, parent -1 for the root) to the strict lower triangle of the
+    (n, n) array D, restated on the host (no GPU).  dict(sums (16 doubles, also by the names of FIT_SUMS), taxon_ss, taxon_pairs,
+    worst (i, j))"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    parent, length, m = _tree_args(n, parent, length)
+    out, ptrs = _fit_out(n)
+    _chk(lib, lib.dpr_tree_fit_host(_p(rows, c_f64p), n, m, _p(parent, c_i32p), _p(length, c_f64p), *ptrs))
+    return _fit_result(out)
+
+
+def tree_fit_derive(sums):
+    """a copy of the 16 sums with the derived figures (entries 11 .. 15) computed from the first eleven"""
+    lib = load_library()
+    s = np.array(sums, dtype=np.float64)
+    assert s.shape == (16,)
+    _chk(lib, lib.dpr_tree_fit_derive(_p(s, c_f64p)))
+    return s
+
+
+def _tree_result(n, parent, length, m):
+    return parent[: m.value], length[: m.value]
+
+
+def tree_from_nj(merge_x, merge_y, bl_x, bl_y, last_d, n=None):
+    """(parent, length) of an NJ / BIONJ merge log (n - 2 entries) with the node bookkeeping of the command's Newick writer: 2n - 1
+    nodes, the two nodes left after the log under the root, each on 0.5 * last_d"""
+    lib = load_library()
+    mx, my = (np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1)) for a in (merge_x, merge_y))
+    bx, by = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)) for a in (bl_x, bl_y))
+    n = len(mx) + 2 if n is None else int(n)
+    assert n < 2 or len(mx) == len(my) == len(bx) == len(by) == n - 2
+    if n == 2:
+        mx = my = np.zeros(1, dtype=np.int32)
+        bx = by = np.zeros(1)
+    parent, length, m = np.zeros(max(2 * n - 1, 1), dtype=np.int32), np.zeros(max(2 * n - 1, 1)), C.c_int64(0)
+    _chk(lib, lib.dpr_tree_from_nj(n, _p(mx, c_i32p), _p(my, c_i32p), _p(bx, c_f64p), _p(by, c_f64p), float(last_d), _p(parent, c_i32p),
+                                   _p(length, c_f64p), C.byref(m)))
+    return _tree_result(n, parent, length, m)
+
+
+def tree_from_kids(kids, top, length):
+    """(parent, length) of the outputs of bme_nni / bme_spr (kids: 2 (n - 2) entries, top, length: 2n - 2 entries): tip n - 1 and top
+    under the root, each on half of length[top]"""
+    lib = load_library()
+    kids = np.ascontiguousarray(np.asarray(kids, dtype=np.int32).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(length, dtype=np.float64).reshape(-1))
+    n = len(ln) // 2 + 1
+    assert len(ln) == 2 * n - 2 and len(kids) == 2 * max(n - 2, 0)
+    if n == 2:
+        kids = np.zeros(1, dtype=np.int32)
+    parent, out, m = np.zeros(2 * n - 1, dtype=np.int32), np.zeros(2 * n - 1), C.c_int64(0)
+    _chk(lib, lib.dpr_tree_from_kids(n, _p(kids, c_i32p), int(top), _p(ln, c_f64p), _p(parent, c_i32p), _p(out, c_f64p), C.byref(m)))
+    return _tree_result(n, parent, out, m)
+
+
+def tree_from_upgma(merge_x, merge_y, height):
+    """(parent, length) of a UPGMA / WPGMA log (n - 1 entries): the rooted tree the command writes, the last merge the root"""
+    lib = load_library()
+    mx, my = (np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1)) for a in (merge_x, merge_y))
+    h = np.ascontiguousarray(np.asarray(height, dtype=np.float64).reshape(-1))
+    n = len(mx) + 1
+    assert len(my) == len(h) == n - 1
+    parent, length, m = np.zeros(max(2 * n - 1, 1), dtype=np.int32), np.zeros(max(2 * n - 1, 1)), C.c_int64(0)
+    _chk(lib, lib.dpr_tree_from_upgma(n, _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p), _p(parent, c_i32p), _p(length, c_f64p), C.byref(m)))
+    return _tree_result(n, parent, length, m)
 
 
 def nj_variant_host(variant, D, max_iters=-1):
@@ -1038,6 +1139,46 @@ class Dipper:
         a = C.c_double()
         _chk(self.L, self.L.dpr_get_upgma_timing(self.h, C.byref(a)))
         return a.value
+
+    def tree_fit(self, parent, length, n=None):
+        """tree_fit_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run); the
+        context's matrix is left as it was"""
+        n = self.n_total() if n is None else int(n)
+        parent, length, m = _tree_args(n, parent, length)
+        out, ptrs = _fit_out(max(n, 1))
+        _chk(self.L, self.L.dpr_tree_fit(self.h, n, m, _p(parent, c_i32p), _p(length, c_f64p), *ptrs))
+        return _fit_result(out)
+
+    def tree_patristic_rows(self, n, parent, length, row0=0, nrows=None):
+        """(nrows, n) array of the tree's path lengths between the tips row0 .. row0 + nrows and every tip, through the device's
+        lowest-common-ancestor lookup; needs no matrix"""
+        nrows = n - row0 if nrows is None else int(nrows)
+        parent, length, m = _tree_args(n, parent, length)
+        out = np.zeros((max(nrows, 1), n))
+        _chk(self.L, self.L.dpr_tree_patristic_rows(self.h, n, m, _p(parent, c_i32p), _p(length, c_f64p), int(row0), nrows, _p(out, c_f64p)))
+        return out[:nrows]
+
+    def fit_stats(self):
+        """dict(bytes held, allocations so far, launches of the last tree_fit, rows of its lookup table)"""
+        out = np.zeros(4, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_fit_stats(self.h, _p(out, c_i64p)))
+        return dict(bytes=int(out[0]), allocations=int(out[1]), launches=int(out[2]), levels=int(out[3]))
+
+    def fit_timing(self):
+        """(ms of the two passes of the last tree_fit, ms of the NJ row-sum kernel beside them or 0 without set_fit_compare(True))"""
+        r, c, b = C.c_double(), C.c_double(), C.c_double()
+        _chk(self.L, self.L.dpr_get_fit_timing(self.h, C.byref(r), C.byref(c), C.byref(b)))
+        return r.value + c.value, b.value
+
+    def fit_pass_timing(self):
+        """(ms of the row pass, ms of the column pass) of the last tree_fit"""
+        r, c = C.c_double(), C.c_double()
+        _chk(self.L, self.L.dpr_get_fit_timing(self.h, C.byref(r), C.byref(c), None))
+        return r.value, c.value
+
+    def set_fit_compare(self, on):
+        """time the NJ row-sum kernel over the same fresh matrix after every tree_fit (measurement aid)"""
+        _chk(self.L, self.L.dpr_ctx_set_fit_compare(self.h, 1 if on else 0))
 
     def transfer_taxa(self, n, main_x, main_y, rep_x, rep_y, cutoff_permille=300, phi_sum=None, moved=None, pairs=None):
         """transfer_taxa_host's numbers, computed on the device"""

@@ -63,6 +63,7 @@ struct dpr_ctx {
     dpr::TbeBuffers tbe;
     dpr::BmeBuffers bme;             // dpr_bme_nni: the table of subtree averages and its small arrays
     dpr::UpgmaBuffers upgma;         // dpr_upgma_run: the working copy of the matrix, the nearest-neighbour cache and the log
+    dpr::FitBuffers fit;             // dpr_tree_fit: the tree's lookup tables and the per-taxon parts
     int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip
     double* packed_lower = nullptr;  // MATRIX source, device

@@ -493,6 +493,22 @@ struct UpgmaBuffers {
     double loop_ms = 0;                  // of the last call: the n - 1 iterations (HIP events)
 };
 
+// ---- fit of a tree to the matrix (fit.hip) ---------------------------------------------------------------------------------------
+// Kept by the context from the first dpr_tree_fit / dpr_tree_patristic_rows on (a later call over no more tips allocates nothing).
+struct FitBuffers {
+    DevBuf<int32_t> rank;                // [cap_n] place of every tip in the depth-first order
+    DevBuf<double> dtip;                 // [cap_n] depth of every tip
+    DevBuf<double> dnode;                // [cap_n] depth of the internal nodes by order index
+    DevBuf<int32_t> tab;                 // [levels][n - 1] sparse table of order indices (cap_levels * cap_n entries held)
+    DevBuf<double> dpart;                // [9][cap_n]: the seven row parts, the row maxima, the column parts of e e; then scratch row sums
+    DevBuf<int32_t> ipart;               // [5][cap_n]: three row counts, the maxima's j, the column counts
+    int64_t cap_n = 0, cap_levels = 0;
+    int64_t allocations = 0;             // device allocations made for this context so far
+    int64_t launches = 0, levels = 0;    // of the last dpr_tree_fit: kernels, rows of its table
+    double row_ms = 0, col_ms = 0, rowsum_ms = 0;      // of the last dpr_tree_fit (HIP events)
+    int compare = 0;                     // dpr_ctx_set_fit_compare: time the NJ row-sum kernel beside the passes
+};
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of kIC = 1 024 tips the (value -> tips, positions) postings
 struct MashIndex {

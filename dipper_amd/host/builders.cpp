@@ -3,8 +3,10 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <chrono>
 #include <condition_variable>
@@ -25,6 +27,65 @@ int& upgmaOption()
 {
     static int linkage = -1;
     return linkage;
+}
+
+FitOption& fitOption()
+{
+    static FitOption o;
+    return o;
+}
+
+// a double with 17 significant digits (round-trips); a NaN of either sign as `nan`
+static std::string fitNumber(double v)
+{
+    if (v != v) return "nan";
+    char buf[40];
+    std::snprintf(buf, sizeof(buf), "%.17g", v);
+    return buf;
+}
+
+void reportFit(DeviceContext& dev, const std::vector<std::string>& name, const std::vector<int32_t>& parent, const std::vector<double>& len)
+{
+    const FitOption& o = fitOption();
+    const size_t n = name.size();
+    double sums[16];
+    std::vector<double> ss(n);
+    std::vector<int64_t> pairs(n);
+    int32_t worst[2] = { -1, -1 };
+    gpuCheck(dpr_tree_fit(dev.ctx, (int64_t)n, (int64_t)parent.size(), parent.data(), len.data(), sums, ss.data(), pairs.data(), worst), "dpr_tree_fit");
+    const std::string none = "-";
+    std::cerr << "Fit: " << (long long)sums[0] << " pairs (" << (long long)sums[1] << " skipped), SS " << fitNumber(sums[7]) << ", rms " << fitNumber(sums[11])
+              << ", relative rms " << fitNumber(sums[12]) << ", explained variance " << fitNumber(sums[13]) << ", cophenetic correlation "
+              << fitNumber(sums[14]) << ", worst pair " << (worst[0] >= 0 ? name[(size_t)worst[0]] : none) << " / "
+              << (worst[1] >= 0 ? name[(size_t)worst[1]] : none) << " (|d - p| = " << fitNumber(sums[10]) << ")\n";
+    // per taxon: rms residual over its counted pairs, and that over the tree-wide rms
+    const double zero = 0.0;
+    std::vector<double> rms(n), rel(n);
+    for (size_t t = 0; t < n; ++t) {
+        rms[t] = pairs[t] > 0 ? std::sqrt(ss[t] / (double)pairs[t]) : zero / zero;
+        rel[t] = rms[t] / sums[11];
+    }
+    std::vector<size_t> order(n);
+    for (size_t t = 0; t < n; ++t) order[t] = t;
+    // largest rms first, NaN last, ties by slot
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return rms[a] == rms[a] && (rms[b] != rms[b] || rms[a] > rms[b]); });
+    std::cerr << "Fit: worst taxa";
+    for (size_t k = 0; k < std::min<size_t>(5, n); ++k)
+        std::cerr << (k ? ", " : " ") << name[order[k]] << " (rms " << fitNumber(rms[order[k]]) << ")";
+    std::cerr << "\n";
+    if (cliLog()) {
+        double row_ms = 0, col_ms = 0;
+        dpr_get_fit_timing(dev.ctx, &row_ms, &col_ms, nullptr);
+        std::cerr << "  device: fit row pass " << row_ms << " ms, column pass " << col_ms << " ms\n";
+    }
+    if (!o.taxa || rankInfo().rank != 0) return;
+    std::ostream& os = *o.taxa;
+    os << "taxon\tpairs\tss\trms\trms_over_tree_rms\n";
+    for (size_t i = 0; i < n; ++i) {
+        const size_t t = o.slotOfInput.empty() ? i : (size_t)o.slotOfInput[i];
+        os << name[t] << "\t" << pairs[t] << "\t" << fitNumber(ss[t]) << "\t" << fitNumber(rms[t]) << "\t" << fitNumber(rel[t]) << "\n";
+    }
+    os.flush();
 }
 
 SiteFilterOption& siteFilterOption()
@@ -295,7 +356,8 @@ void NJDeviceArrays::getDismatrix(DeviceContext& dev, int numSequences, Param& p
     }
 }
 
-void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_)
+void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_, Param* params,
+                                              MatrixReader* matrixReader)
 {
     const int N = d_numSequences;
     std::vector<int32_t> mx((size_t)std::max(N - 2, 1)), my((size_t)std::max(N - 2, 1));
@@ -312,6 +374,18 @@ void NJDeviceArrays::findNeighbourJoiningTree(DeviceContext& dev, std::vector<st
         std::cerr << "  device: distances " << dist_ms << " ms, NJ " << nj_ms << " ms; dpr_nj_run call "
                   << std::chrono::duration<double, std::milli>(t1 - t0).count() << " ms; Newick text "
                   << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() << " ms\n";
+    }
+    if (fitOption().on && params) {
+        output_.flush();
+        // the NJ run consumed the matrix: the fit reads a fresh one.  No NJ run follows, so it is built under the streaming plan: in slot
+        // space, where both passes of the fit read coalesced, and without the pruned plan's first epoch
+        gpuCheck(dpr_ctx_set_nj_mode(dev.ctx, 0), "dpr_ctx_set_nj_mode");
+        getDismatrix(dev, N, *params, matrixReader);
+        std::vector<int32_t> parent((size_t)(2 * N - 1));
+        std::vector<double> len((size_t)(2 * N - 1));
+        int64_t m = 0;
+        gpuCheck(dpr_tree_from_nj(N, mx.data(), my.data(), bx.data(), by.data(), last, parent.data(), len.data(), &m), "dpr_tree_from_nj");
+        reportFit(dev, name, parent, len);
     }
 }
 
@@ -330,6 +404,14 @@ void NJDeviceArrays::findUpgmaTree(DeviceContext& dev, std::vector<std::string>&
         double loop_ms = 0;
         dpr_get_upgma_timing(dev.ctx, &loop_ms);
         std::cerr << "  device: " << (linkage ? "WPGMA" : "UPGMA") << " loop " << loop_ms << " ms, " << stats[2] << " launches\n";
+    }
+    if (fitOption().on) {      // (dpr_upgma_run works on a copy: the matrix is still fresh)
+        output_.flush();
+        std::vector<int32_t> parent((size_t)(2 * N - 1));
+        std::vector<double> len((size_t)(2 * N - 1));
+        int64_t m = 0;
+        gpuCheck(dpr_tree_from_upgma(N, mx.data(), my.data(), h.data(), parent.data(), len.data(), &m), "dpr_tree_from_upgma");
+        reportFit(dev, name, parent, len);
     }
 }
 
@@ -363,6 +445,14 @@ void NJDeviceArrays::findRefinedTree(DeviceContext& dev, Param& params, MatrixRe
             std::cerr << ", SPR scans " << scan_ms << " ms";
         }
         std::cerr << "\n";
+    }
+    if (fitOption().on) {      // (the search read the fresh matrix and left it so)
+        output_.flush();
+        std::vector<int32_t> parent((size_t)(2 * N - 1));
+        std::vector<double> flen((size_t)(2 * N - 1));
+        int64_t m = 0;
+        gpuCheck(dpr_tree_from_kids(N, kids.data(), top, len.data(), parent.data(), flen.data(), &m), "dpr_tree_from_kids");
+        reportFit(dev, name, parent, flen);
     }
 }
 

@@ -139,6 +139,19 @@ bool& bionjOption();
 // -1 = NJ.  Set by main() before the first tree
 int& upgmaOption();
 
+// --fit [--fit-taxa FILE]: after the tree is written, the fit of that tree to a FRESH distance matrix (dpr_tree_fit): one `Fit:` line
+// and the five worst taxa on stderr, the per-taxon table to FILE.  Set by main() before the first tree.
+struct FitOption {
+    bool on = false;
+    std::string taxaFile;                // --fit-taxa, or empty
+    std::ofstream* taxa = nullptr;       // that file, opened by main() before the tree is built
+    std::vector<int> slotOfInput;        // slot of the taxon read i-th (the table lists the taxa in input order); empty: slot = input order
+};
+struct DeviceContext;
+FitOption& fitOption();
+// The fit of the tree (parent, len over 2n - 1 nodes, tips = slots) to the context's fresh matrix, reported as above.  name: by slot.
+void reportFit(DeviceContext& dev, const std::vector<std::string>& name, const std::vector<int32_t>& parent, const std::vector<double>& len);
+
 // --site-coverage X / --complete-deletion (-i m): every alignment this command uploads -- the three MSADeviceArrays uploads and the
 // bootstrap's rank-local context -- keeps only the columns in which at least X of the sequences hold a symbol
 // (dpr_msa_filter_sites).  Set by main() before the first upload.
@@ -197,7 +210,9 @@ struct MSADeviceArrays {  // src/mash_placement.cuh:87-98
 struct NJDeviceArrays {  // src/mash_placement.cuh:199-212
     int d_numSequences = 0;
     void getDismatrix(DeviceContext& dev, int numSequences, Param& params, MatrixReader* matrixReader);
-    void findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_);
+    // params / matrixReader: what getDismatrix took; read with --fit only, which builds the matrix the NJ run consumed again
+    void findNeighbourJoiningTree(DeviceContext& dev, std::vector<std::string>& name, std::ostream& output_, Param* params = nullptr,
+                                  MatrixReader* matrixReader = nullptr);
     // --nni R: the NJ / BIONJ tree as above, the distance matrix built again, at most R rounds of balanced minimum evolution NNI
     // on it (dpr_bme_nni) and the tree it ends on with its balanced branch lengths; one line on stderr.  spr (--spr R): the SPR
     // search of dpr_bme_spr in its place

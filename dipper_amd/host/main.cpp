@@ -122,6 +122,21 @@ static const char* kHelp =
     "                              -m 1, -m 3, --add, -o d, -o j or several ranks\n"
     "  --wpgma                     As --upgma with WPGMA: a merged cluster's distances are the plain mean of\n"
     "                              its two parts' (McQuitty's weighted linkage).  Not together with --upgma\n"
+    "  --fit                       After the tree is written, report how well it explains the distances: over all\n"
+    "                              pairs of taxa the residual of the distance against the tree's path length --\n"
+    "                              one line `Fit:` on stderr with the pairs counted (a pair with a non-finite\n"
+    "                              distance or path length is skipped), the sum of squares, the rms residual, the\n"
+    "                              relative rms (PHYLIP's average percent standard deviation / 100), the explained\n"
+    "                              variance (FastME), the cophenetic correlation and the worst pair; a second line\n"
+    "                              names the five taxa with the largest rms residual.  Computed on the GPU from a\n"
+    "                              fresh distance matrix; the tree file is unchanged.  Valid where --nni is (-m 2,\n"
+    "                              or -m 0 below 30000; -i d, m or r; --protein; every -d; --site-coverage; one\n"
+    "                              GPU), with --bionj, --nni, --spr, --upgma and --wpgma.  Not with -m 1, -m 3,\n"
+    "                              --add, -o d, -o j, --bootstrap or several ranks\n"
+    "  --fit-taxa arg              Write the per-taxon residuals to file arg: a header line, then for every taxon\n"
+    "                              in input order its counted pairs, residual sum of squares, rms residual and\n"
+    "                              that rms over the tree-wide rms (tab-separated, 17 significant digits).\n"
+    "                              Needs --fit\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -151,7 +166,7 @@ static const Opt kOpts[] = {
     { "bootstrap", 0, true }, { "bootstrap-seed", 0, true }, { "bootstrap-metric", 0, true },
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
     { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
-    { "site-coverage", 0, true }, { "complete-deletion", 0, false },
+    { "site-coverage", 0, true }, { "complete-deletion", 0, false }, { "fit", 0, false }, { "fit-taxa", 0, true }, { "dump-newick", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -232,6 +247,40 @@ int main(int argc, char** argv)
         for (const Node& nd : t.nodes)
             std::printf("%d %d %.17g %d %s\n", nd.idx, nd.parent >= 0 ? t.nodes[(size_t)nd.parent].idx : -1, nd.bl,
                         nd.children.empty() ? 1 : 0, nd.name.c_str());
+        return 0;
+    }
+    if (vm.count("dump-newick")) {
+        // developer aid (no GPU): the three Newick writers on a log from a text file, tips named t0, t1, ...; the text goes to stdout.
+        // First line `nj N last`, then N - 2 lines `x y bx by`; or `upgma N`, then N - 1 lines `x y h`; or `kids N top`, then the
+        // 2 (N - 2) children and the 2N - 2 lengths.  Numbers through strtod (hexadecimal floats are read exactly).
+        std::ifstream lf(vm["dump-newick"]);
+        if (!lf) { std::cerr << "ERROR: cant open file: " << vm["dump-newick"] << "\n"; return 1; }
+        std::string kind, tok;
+        long long N = 0;
+        if (!(lf >> kind >> N) || N < 2 || N > 100000) die("ERROR: --dump-newick: first line `nj N last`, `upgma N` or `kids N top`");
+        auto num = [&]() { if (!(lf >> tok)) die("ERROR: --dump-newick: the file ends early"); return std::strtod(tok.c_str(), nullptr); };
+        std::vector<std::string> names;
+        for (long long i = 0; i < N; ++i) names.push_back("t" + std::to_string(i));
+        const size_t merges = (size_t)(kind == "upgma" ? N - 1 : N - 2);
+        std::vector<int32_t> mx(merges), my(merges);
+        std::vector<double> a(merges), b(merges);
+        if (kind == "nj") {
+            const double last = num();
+            for (size_t it = 0; it < merges; ++it) { mx[it] = (int32_t)num(); my[it] = (int32_t)num(); a[it] = num(); b[it] = num(); }
+            writeNewickFromMerges(std::cout, names, mx, my, a, b, last);
+        } else if (kind == "upgma") {
+            for (size_t it = 0; it < merges; ++it) { mx[it] = (int32_t)num(); my[it] = (int32_t)num(); a[it] = num(); }
+            writeNewickFromUpgma(std::cout, names, mx, my, a);
+        } else if (kind == "kids") {
+            const int32_t top = (int32_t)num();
+            std::vector<int32_t> kids(2 * merges);
+            std::vector<double> len((size_t)(2 * N - 2));
+            for (int32_t& k : kids) k = (int32_t)num();
+            for (double& v : len) v = num();
+            writeNewickFromKids(std::cout, names, kids, top, len);
+        } else {
+            die("ERROR: --dump-newick: first line `nj N last`, `upgma N` or `kids N top`");
+        }
         return 0;
     }
     if (vm.count("dump-lengths")) {
@@ -368,6 +417,22 @@ int main(int argc, char** argv)
         if (out == "d" || out == "j") usageError(cluster + " needs tree output (-o t)");
         upgmaOption() = upgma;
     }
+    // --fit / --fit-taxa: what the arguments alone decide, before any input is read or a GPU touched (several ranks: below)
+    const bool fit = vm.count("fit") != 0;
+    if (vm.count("fit-taxa") && !fit) usageError("--fit-taxa needs --fit");
+    if (fit) {
+        const std::string al = strOr(vm, "algorithm", "0"), out = strOr(vm, "output-format", "t");
+        if (al == "1" || al == "3") usageError("--fit needs conventional NJ (-m 2, or the default mode below 30000 sequences)");
+        if (vm.count("add")) usageError("--fit is not supported with --add");
+        if (out == "d" || out == "j") usageError("--fit needs tree output (-o t)");
+        if (vm.count("bootstrap")) usageError("--fit is not supported with --bootstrap (one tree, one matrix)");
+        if (vm.count("fit-taxa")) {
+            if (vm["fit-taxa"].empty()) usageError("--fit-taxa: a file name");
+            if (vm["fit-taxa"] == vm["output-file"]) usageError("--fit-taxa: the file must differ from the output file (-O)");
+            fitOption().taxaFile = vm["fit-taxa"];
+        }
+        fitOption().on = true;
+    }
     if (vm.count("add") && !vm.count("input-tree"))
         usageError("Backbone tree (--input-tree/-t) is required with --add option");
     // --protein: what the arguments alone decide, before any input is read or a GPU touched
@@ -502,6 +567,8 @@ int main(int argc, char** argv)
         usageError(refine + " runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
     if (upgma >= 0 && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
         usageError(cluster + " runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
+    if (fit && (multi || ranks.devices.size() > 1 || vm.count("rank") || vm.count("world")))
+        usageError("--fit runs on one GPU (not with --gpus above 1, several --devices or --rank / --world)");
     if (!multi && ranks.devices.size() == 1) device = ranks.devices[0];      // (`--devices 3` alone: one rank on GPU 3)
 
     const int placement_thr = 30000, dc_thr = 1000000;  // src/tree_generation.cu:247-248
@@ -513,6 +580,14 @@ int main(int argc, char** argv)
         auto os = std::make_unique<std::ofstream>(rankInfo().rank == 0 ? outputFile.c_str() : "/dev/null");
         if (!*os) die("ERROR: cannot open output file: " + outputFile);
         return os;
+    };
+    // --fit-taxa: opened before the tree is built, so that a path that cannot be written ends the run there
+    std::unique_ptr<std::ofstream> fitTaxaOut;
+    auto open_fit_taxa = [&]() {
+        if (fitOption().taxaFile.empty()) return;
+        fitTaxaOut = std::make_unique<std::ofstream>(fitOption().taxaFile.c_str());
+        if (!*fitTaxaOut) die("ERROR: cannot open the --fit-taxa file: " + fitOption().taxaFile);
+        fitOption().taxa = fitTaxaOut.get();
     };
     // mode selection of the reference (src/tree_generation.cu:377,422,450): 1 = placement, 3 = DC, 2 = NJ
     auto pick_mode = [&](long long n) {
@@ -753,11 +828,15 @@ int main(int argc, char** argv)
         if (upgma >= 0 && pick_mode((long long)numSequences) != 2)
             die("ERROR: " + cluster + " builds the tree where conventional NJ does: " + std::to_string(numSequences) + " sequences select " +
                 (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (fit && pick_mode((long long)numSequences) != 2)
+            die("ERROR: --fit needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (pick_mode((long long)numSequences) == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (protein && pick_mode((long long)numSequences) == 3)
             die("ERROR: divide-and-conquer is not available with --protein: " + std::to_string(numSequences) +
                 " sequences select it in the default mode; use -m 1 or -m 2");
         if (multi) { startRanks(ranks, device); adev.reset(new AsyncDeviceContext(rankInfo().device)); }
         auto output_ = open_out();
+        if (fit) { open_fit_taxa(); fitOption().slotOfInput = shuffledIds(numSequences, seed); }
         std::unique_ptr<std::ofstream> taxaOut;
         if (!taxaFile.empty()) {
             // (opened before the main tree is built: a path that cannot be written ends the run here; rank 0 writes the report)
@@ -839,7 +918,7 @@ int main(int argc, char** argv)
             } else if (upgma >= 0) {
                 njDeviceArrays.findUpgmaTree(dev, names, *output_, upgma);
             } else {
-                njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_);
+                njDeviceArrays.findNeighbourJoiningTree(dev, names, *output_, &params, nullptr);
             }
             std::cerr << "Tree Created in: " << ms_since(t0) << " ms\n";
         }
@@ -847,6 +926,7 @@ int main(int argc, char** argv)
         // the tree is written: close the output and leave without running the static destructors of the HIP runtime
         output_.reset();
         taxaOut.reset();
+        fitTaxaOut.reset();
         if (cliLog()) std::cerr << "Main in: " << ms_since(inputStart) << " ms\n";
         std::cerr.flush();
         std::fflush(nullptr);
@@ -874,9 +954,13 @@ int main(int argc, char** argv)
         if (upgma >= 0 && mode != 2)
             die("ERROR: " + cluster + " builds the tree where conventional NJ does: " + std::to_string(numSequences) + " sequences select " +
                 (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
+        if (fit && mode != 2)
+            die("ERROR: --fit needs conventional NJ: " + std::to_string(numSequences) + " sequences select " +
+                (mode == 1 ? "placement" : "divide-and-conquer") + " in the default mode; use -m 2");
         if (mode == 3) { std::cerr << "Divide-and-conquer mode not supported with input matrix\n"; return 1; }
         if (multi) startRanks(ranks, device);
         auto output_ = open_out();
+        if (fit) open_fit_taxa();
         DeviceContext dev(multi ? rankInfo().device : device);
         if (mode == 1) {
             std::cerr << "Using " << (exact_mode ? " exact placement mode\n" : "k-closest placement mode\n");
@@ -895,7 +979,7 @@ int main(int argc, char** argv)
             njDeviceArrays.getDismatrix(dev, numSequences, params, &matrixReader);
             if (nni >= 0) njDeviceArrays.findRefinedTree(dev, params, &matrixReader, matrixReader.name, *output_, nni, spr);
             else if (upgma >= 0) njDeviceArrays.findUpgmaTree(dev, matrixReader.name, *output_, upgma);
-            else njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_);
+            else njDeviceArrays.findNeighbourJoiningTree(dev, matrixReader.name, *output_, &params, &matrixReader);
         }
         printRankSummary(dev.ctx);
     } else {

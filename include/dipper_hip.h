@@ -753,6 +753,68 @@ int dpr_get_upgma_stats(dpr_ctx *ctx, int64_t *out4);
 /* of the last dpr_upgma_run: its n - 1 iterations (HIP events; the copy of the matrix and the first fill of the cache are outside) */
 int dpr_get_upgma_timing(dpr_ctx *ctx, double *loop_ms);
 
+/* ---- Fit of a tree to the distance matrix: residuals of the distances against the tree's path lengths (FastME's explained
+ * variance, PHYLIP's sum of squares and average percent standard deviation, the cophenetic correlation, per-taxon residuals) ------
+ * The tree as arrays.  m nodes, n + 1 <= m <= 2n - 1, the tips are nodes 0 .. n-1.  parent[m]: the parent of every node, -1 for the
+ *   one root; len[m]: the edge above every node (the root's entry is ignored).  Internal nodes have two children or more.  Not a
+ *   tree -- no root or several, a tip with children (the root a tip included), a parent outside n .. m-1, an internal node with fewer
+ *   than two children, a cycle, a node the root does not reach -- is DPR_ERR_ARG.
+ * Arithmetic contract (fp64, exactly this order of operations, no contraction; the device and dpr_tree_fit_host produce the same
+ * bits).
+ * Depths.  depth[root] = 0, depth[v] = depth[parent[v]] + len[v].
+ * Path length.  P_ij = (depth[i] - depth[a]) + (depth[j] - depth[a]), a = lca(i, j).
+ * Pairs.  {i, j}, i > j, with D_ij the matrix entry, is COUNTED iff D_ij and P_ij are both finite; otherwise it is skipped, adds to
+ *   nothing and is tallied.  e = D - P.  Terms of a counted pair: D, P, D * D, P * P, D * P, e * e, and (e * e) / (D * D) if D > 0
+ *   (a counted pair with D <= 0 adds to everything but that last sum and its count N_w).
+ * Row part of taxon i, one per sum.  256 accumulators start at +0.0; the term of {i, j}, j < i, is added to accumulator j mod 256, j
+ *   ascending; then c[t] = c[t] + c[t + s] for t < s, s = 128, 64 .. 1; the part is c[0].
+ * Column part of taxon j, for e * e only.  16 accumulators; the term of {i, j}, i > j, is added to accumulator i mod 16, i ascending;
+ *   then c[t] = c[t] + c[t + s] for t < s, s = 8, 4, 2, 1; the part is c[0].
+ * Totals.  Every sum starts at +0.0 and adds its row parts over i = 0 .. n-1 ascending.  taxon_ss[t] = row part + column part of
+ *   e * e; taxon_pairs[t] the counted pairs that hold t.  The largest |e| over the counted pairs, ties to the smaller i and then the
+ *   smaller j.  Nothing depends on a launch geometry; there are no floating-point atomics.
+ * sums[16]: 0 N counted pairs, 1 skipped pairs, 2 sum D, 3 sum P, 4 sum D D, 5 sum P P, 6 sum D P, 7 SS = sum e e, 8 WSS =
+ *   sum e e / (D D), 9 N_w, 10 max |e| (0 without a counted pair), then the derived figures (dpr_tree_fit_derive): 11 rms =
+ *   sqrt(SS / N), 12 relative rms = sqrt(WSS / N_w), 13 explained variance 1 - SS / (sum D D - (sum D * sum D) / N), 14 cophenetic
+ *   correlation (N sum D P - sum D sum P) / sqrt((N sum D D - sum D sum D) * (N sum P P - sum P sum P)); a zero denominator
+ *   gives NaN; 15 is 0.  worst[2]: the pair (i, j), i > j, of max |e|, or (-1, -1). */
+/* On the device (fit.hip).  Reads the context's FRESH matrix as dpr_bme_nni does -- after dpr_dist_matrix, before any NJ iteration,
+ * in whatever layout the context's NJ plan gave it -- else DPR_ERR_STATE; the matrix is left as it was.  n other than the matrix's,
+ * a malformed tree, several ranks, virtual ranks or virtual shards: DPR_ERR_ARG, and the context stays usable.  lca(i, j) is looked
+ * up in a sparse table over the depth-first order of the tips, built on the host and uploaded (4 (n - 1) (floor(log2(n - 1)) + 1)
+ * bytes).  The context keeps its buffers: a later call over no more tips allocates nothing.  taxon_ss, taxon_pairs: n entries. */
+int dpr_tree_fit(dpr_ctx *ctx, int64_t n, int64_t m, const int32_t *parent, const double *len, double *sums, double *taxon_ss,
+                 int64_t *taxon_pairs, int32_t *worst);
+/* host only, no GPU: the contract restated with lca(i, j) found by climbing the parent array from both tips -- on purpose not the
+ * device's lookup -- the reference of the GPU tests.  lower_rows: the strict lower triangle row by row. */
+int dpr_tree_fit_host(const double *lower_rows, int64_t n, int64_t m, const int32_t *parent, const double *len, double *sums,
+                      double *taxon_ss, int64_t *taxon_pairs, int32_t *worst);
+/* host only: sums[11 .. 15] from sums[0 .. 10] -- the one place the derived figures are computed */
+int dpr_tree_fit_derive(double *sums);
+/* P[row0 .. row0 + nrows)[0 .. n) into out (nrows * n doubles, host memory), through the device's lookup; the diagonal by the same
+ * formula with a = i.  Needs no matrix.  The rows' device buffer is allocated for the call and released with it. */
+int dpr_tree_patristic_rows(dpr_ctx *ctx, int64_t n, int64_t m, const int32_t *parent, const double *len, int64_t row0, int64_t nrows,
+                            double *out);
+/* host only: the trees of the builders as arrays, with the node bookkeeping of the command's Newick writers; all give *m = 2n - 1
+ * nodes, the root last; parent, len: 2n - 1 entries.  n < 2, a null pointer, an input that is no log / no tree: DPR_ERR_ARG.
+ * from_nj: the log of dpr_nj_run (n - 2 merges; merge it makes node n + it above the nodes of slots x and y); the two nodes left hang
+ *   from the root, EACH on a branch of 0.5 * last -- neither child carries the whole of `last`.
+ * from_kids: the outputs of dpr_bme_nni / dpr_bme_spr; tip n - 1 and top hang from the root, each on 0.5 * len_in[top].
+ * from_upgma: the log of dpr_upgma_run (n - 1 merges; branches h - h[x], h - h[y]); the last merge is the root. */
+int dpr_tree_from_nj(int64_t n, const int32_t *merge_x, const int32_t *merge_y, const double *bx, const double *by, double last,
+                     int32_t *parent, double *len, int64_t *m);
+int dpr_tree_from_kids(int64_t n, const int32_t *kids, int32_t top, const double *len_in, int32_t *parent, double *len, int64_t *m);
+int dpr_tree_from_upgma(int64_t n, const int32_t *merge_x, const int32_t *merge_y, const double *height, int32_t *parent, double *len,
+                        int64_t *m);
+/* out4: bytes the context holds for dpr_tree_fit, device allocations it has made for this context so far, kernel launches of the
+ * last call, rows of its sparse table */
+int dpr_get_fit_stats(dpr_ctx *ctx, int64_t *out4);
+/* of the last dpr_tree_fit: the row pass, the column pass (HIP events; the upload of the tree is outside; any may be NULL).
+ * rowsum_ms: when dpr_ctx_set_fit_compare(ctx, 1) was called before, the time of the NJ row-sum kernel over the same fresh matrix,
+ * launched once after the two passes into a scratch vector -- the yardstick of tools/fit_bench.py; else 0. */
+int dpr_get_fit_timing(dpr_ctx *ctx, double *row_ms, double *col_ms, double *rowsum_ms);
+int dpr_ctx_set_fit_compare(dpr_ctx *ctx, int on);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
