@@ -15,6 +15,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "merge_log.hpp"
+
 #if defined(__HIPCC__)
 #define DPR_BME_HD __host__ __device__
 #else
@@ -96,28 +98,22 @@ struct Tree {
     View view() const { return View{ kid0.data(), kid1.data(), par.data(), sib.data(), height.data(), tin.data(), tout.data(), t0, top, nullptr }; }
 };
 
-// the tree of a merge log (the realID bookkeeping of writeNewickFromMerges), hung from tip n - 1; false: not a merge log
+// the tree of a merge log (merge_log.hpp, the strict rule), hung from tip n - 1; false: not a merge log
 inline bool from_merges(int64_t n, const int32_t* mx, const int32_t* my, Tree& t)
 {
     const int64_t M = 2 * n - 2;
     t.n = n; t.M = M; t.t0 = (int32_t)(n - 1);
-    std::vector<int32_t> nb((size_t)(3 * M), -1), deg((size_t)M, 0), real((size_t)n);
+    std::vector<int32_t> nb((size_t)(3 * M), -1), deg((size_t)M, 0), real;
+    bool linked = true;
     auto link = [&](int32_t a, int32_t b) {
-        if (deg[(size_t)a] >= 3 || deg[(size_t)b] >= 3) return false;
+        if (deg[(size_t)a] >= 3 || deg[(size_t)b] >= 3) { linked = false; return; }
         nb[(size_t)(3 * a + deg[(size_t)a]++)] = b;
         nb[(size_t)(3 * b + deg[(size_t)b]++)] = a;
-        return true;
     };
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int32_t x = mx[it], y = my[it];
-        if (x < 0 || y <= x || y >= n - it) return false;
-        const int32_t node = (int32_t)(n + it);
-        if (!link(node, real[(size_t)x]) || !link(node, real[(size_t)y])) return false;
-        real[(size_t)x] = node;
-        real[(size_t)y] = real[(size_t)(n - it - 1)];
-    }
-    if (!link(real[0], real[1])) return false;
+    if (!merge_log::replay<true>(n, n - 2, mx, my, real, [&](int64_t, int32_t node, int32_t u, int32_t v) { link(node, u); link(node, v); }))
+        return false;
+    link(real[0], real[1]);
+    if (!linked) return false;
     t.kid0.assign((size_t)M, -1); t.kid1.assign((size_t)M, -1); t.par.assign((size_t)M, -1);
     t.top = nb[(size_t)(3 * t.t0)];
     t.par[(size_t)t.t0] = t.top; t.par[(size_t)t.top] = t.t0;

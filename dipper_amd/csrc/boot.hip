@@ -15,6 +15,7 @@
 // dpr_split_support (host) counts the main tree's splits in a replicate tree from the two merge logs; dpr_comm_sum_i32 sums
 // the counts over the ranks.
 #include "ctx_internal.hpp"
+#include "merge_log.hpp"
 
 #include <algorithm>
 
@@ -126,7 +127,6 @@ struct Clades {
     std::vector<int32_t> size;
     std::vector<uint8_t> has0;
     uint64_t ta = 0, tb = 0;        // all tips
-    int32_t root0 = -1, root1 = -1; // the two children of the NJ root
 };
 static bool clades_of(int64_t n, const int32_t* mx, const int32_t* my, Clades& c)
 {
@@ -140,21 +140,12 @@ static bool clades_of(int64_t n, const int32_t* mx, const int32_t* my, Clades& c
         c.ta ^= c.a[(size_t)t]; c.tb ^= c.b[(size_t)t];
     }
     c.has0[0] = 1;
-    std::vector<int32_t> real((size_t)n);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    // realID bookkeeping of writeNewickFromMerges (src/neighborJoining.cu:233-237)
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int32_t x = mx[it], y = my[it];
-        if (x < 0 || y <= x || y >= n - it) return false;
-        const size_t id = (size_t)(n + it), u = (size_t)real[(size_t)x], v = (size_t)real[(size_t)y];
-        c.a[id] = c.a[u] ^ c.a[v]; c.b[id] = c.b[u] ^ c.b[v];
-        c.size[id] = c.size[u] + c.size[v];
-        c.has0[id] = c.has0[u] | c.has0[v];
-        real[(size_t)x] = (int32_t)id;
-        real[(size_t)y] = real[(size_t)(n - it - 1)];
-    }
-    c.root0 = real[0]; c.root1 = n > 1 ? real[1] : -1;
-    return true;
+    std::vector<int32_t> real;
+    return merge_log::replay<true>(n, n - 2, mx, my, real, [&](int64_t, int32_t id, int32_t u, int32_t v) {
+        c.a[(size_t)id] = c.a[(size_t)u] ^ c.a[(size_t)v]; c.b[(size_t)id] = c.b[(size_t)u] ^ c.b[(size_t)v];
+        c.size[(size_t)id] = c.size[(size_t)u] + c.size[(size_t)v];
+        c.has0[(size_t)id] = c.has0[(size_t)u] | c.has0[(size_t)v];
+    });
 }
 
 }  // namespace dpr

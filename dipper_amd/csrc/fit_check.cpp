@@ -17,7 +17,7 @@ static double rnd()
 
 struct Arrays { std::vector<int32_t> parent; std::vector<double> len; int64_t m = 0; };
 
-// a random merge log over n slots with the realID bookkeeping: `merges` entries
+// a random merge log over n slots (merge_log.hpp): `merges` entries
 static void random_log(int64_t n, int64_t merges, std::vector<int32_t>& mx, std::vector<int32_t>& my)
 {
     mx.assign((size_t)(merges > 0 ? merges : 1), 0); my.assign(mx.size(), 1);

@@ -10,6 +10,8 @@
 
 #include <vector>
 
+#include "merge_log.hpp"
+
 #if defined(__HIPCC__)
 #define FIT_HD __host__ __device__
 #else
@@ -248,28 +250,16 @@ inline int fit_host(const double* lower_rows, int64_t n, int64_t m, const int32_
     return 0;
 }
 
-// ---- converters: the node bookkeeping of the command's Newick writers ------------------------------------------------------------
+// ---- converters: the node bookkeeping of the command's Newick writers (merge_log.hpp) ------------------------------------------------
 // All three give m = 2n - 1 nodes with the root last.  0, or -1 for a bad argument / an input that is no log or tree of its kind.
 
-// NJ / BIONJ log (n - 2 merges, the realID bookkeeping of the log): merge it makes node n + it above the nodes of slots x and y on
-// branches bx, by; the two nodes left hang from the root 2n - 2, EACH on half of `last`
+// NJ / BIONJ log (n - 2 merges, the lenient rule): merge_log::nj_edges, every edge written as parent[child], len[child]
 inline int from_nj(int64_t n, const int32_t* mx, const int32_t* my, const double* bx, const double* by, double last, int32_t* parent, double* len,
                    int64_t* m)
 {
     if (n < 2 || n >= ((int64_t)1 << 24) || !parent || !len || !m || (n > 2 && (!mx || !my || !bx || !by))) return -1;
-    std::vector<int32_t> real((size_t)n);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int64_t x = mx[it], y = my[it], live = n - it;
-        if (x < 0 || y < 0 || x >= live || y >= live || x == y) return -1;
-        const int32_t id = (int32_t)(n + it);
-        parent[real[(size_t)x]] = id; len[real[(size_t)x]] = bx[it];
-        parent[real[(size_t)y]] = id; len[real[(size_t)y]] = by[it];
-        real[(size_t)x] = id;
-        real[(size_t)y] = real[(size_t)(live - 1)];
-    }
-    const int32_t root = (int32_t)(2 * n - 2);
-    for (int s = 0; s < 2; ++s) { parent[real[(size_t)s]] = root; len[real[(size_t)s]] = last * 0.5; }
+    if (!merge_log::nj_edges<false>(n, mx, my, bx, by, last, [&](int32_t p, int, int32_t c, double l) { parent[c] = p; len[c] = l; })) return -1;
+    const int64_t root = 2 * n - 2;
     parent[root] = -1; len[root] = 0.0;
     *m = 2 * n - 1;
     return 0;
@@ -298,24 +288,11 @@ inline int from_kids(int64_t n, const int32_t* kids, int32_t top, const double* 
     return 0;
 }
 
-// UPGMA / WPGMA log (n - 1 merges with heights): merge it makes node n + it above the nodes of slots x and y on branches
-// h - height of each; the last merge is the root
+// UPGMA / WPGMA log (n - 1 merges with heights, the lenient rule): merge_log::upgma_edges, the last merge the root
 inline int from_upgma(int64_t n, const int32_t* mx, const int32_t* my, const double* height, int32_t* parent, double* len, int64_t* m)
 {
     if (n < 2 || n >= ((int64_t)1 << 24) || !mx || !my || !height || !parent || !len || !m) return -1;
-    std::vector<int32_t> real((size_t)n);
-    std::vector<double> h((size_t)n, 0.0);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 1; ++it) {
-        const int64_t x = mx[it], y = my[it], live = n - it;
-        if (x < 0 || y < 0 || x >= live || y >= live || x == y) return -1;
-        const int32_t id = (int32_t)(n + it);
-        const double hn = height[it];
-        parent[real[(size_t)x]] = id; len[real[(size_t)x]] = hn - h[(size_t)x];
-        parent[real[(size_t)y]] = id; len[real[(size_t)y]] = hn - h[(size_t)y];
-        real[(size_t)x] = id; h[(size_t)x] = hn;
-        real[(size_t)y] = real[(size_t)(live - 1)]; h[(size_t)y] = h[(size_t)(live - 1)];
-    }
+    if (!merge_log::upgma_edges<false>(n, mx, my, height, [&](int32_t p, int, int32_t c, double l) { parent[c] = p; len[c] = l; })) return -1;
     const int64_t root = 2 * n - 2;
     parent[root] = -1; len[root] = 0.0;
     *m = 2 * n - 1;

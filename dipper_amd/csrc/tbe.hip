@@ -25,6 +25,7 @@
 // dpr_transfer_support_host restates phi without intervals: per main node, |A & L_v| for every replicate node bottom-up in
 // merge order, then the min of delta over all of them (leaves included).  dpr_comm_sum_i64 sums the phi over the ranks.
 #include "ctx_internal.hpp"
+#include "merge_log.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -204,31 +205,16 @@ __global__ __launch_bounds__(kThreads) void tbe_moved_kernel(const int2* __restr
         if (t[q] < n && cnt[q]) atomicAdd(&moved[t[q]], (int32_t)cnt[q]);
 }
 
-// DFS leaf order of a merge log (the realID bookkeeping of writeNewickFromMerges names internal node n+it after iteration
-// it): the clade of node v (< 2n-2) is [pos[v], pos[v] + size[v]); kid[2 it], kid[2 it + 1] are the children of n+it.
-struct Dfs {
-    std::vector<int32_t> pos, size, kid;
-    int32_t root[2] = { 0, 1 };          // the two nodes the root joins
+// DFS leaf order of a merge log (merge_log.hpp, the strict rule): the clade of node v (< 2n-2) is [pos[v], pos[v] + size[v]).
+struct Dfs : merge_log::Sizes {
+    std::vector<int32_t> pos;
 };
 static bool dfs_of(int64_t n, const int32_t* mx, const int32_t* my, Dfs& d)
 {
-    const int64_t nodes = 2 * n - 2;
-    d.pos.assign((size_t)nodes, 0); d.size.assign((size_t)nodes, 1); d.kid.assign((size_t)(2 * std::max<int64_t>(n - 2, 0)), 0);
-    std::vector<int32_t> real((size_t)n);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int32_t x = mx[it], y = my[it];
-        if (x < 0 || y <= x || y >= n - it) return false;
-        const int32_t u = real[(size_t)x], v = real[(size_t)y];
-        d.kid[(size_t)(2 * it)] = u; d.kid[(size_t)(2 * it + 1)] = v;
-        d.size[(size_t)(n + it)] = d.size[(size_t)u] + d.size[(size_t)v];
-        real[(size_t)x] = (int32_t)(n + it);
-        real[(size_t)y] = real[(size_t)(n - it - 1)];
-    }
-    // the root joins real[0] and real[1]; every other node has a parent with a larger number
-    d.root[0] = real[0]; d.root[1] = real[1];
-    d.pos[(size_t)real[0]] = 0;
-    d.pos[(size_t)real[1]] = d.size[(size_t)real[0]];
+    if (!merge_log::sizes_of<true>(n, mx, my, d)) return false;
+    // the root joins root[0] and root[1]; every other node has a parent with a larger number
+    d.pos.assign((size_t)(2 * n - 2), 0);
+    d.pos[(size_t)d.root[1]] = d.size[(size_t)d.root[0]];
     for (int64_t it = n - 3; it >= 0; --it) {
         const int32_t v = (int32_t)(n + it), a = d.kid[(size_t)(2 * it)], b = d.kid[(size_t)(2 * it + 1)];
         d.pos[(size_t)a] = d.pos[(size_t)v];

@@ -320,7 +320,7 @@ inline bool cliLog()
     return s.find(",cli,") != std::string::npos || s.find(",cli=") != std::string::npos;
 }
 
-// Newick text of an NJ merge log (bookkeeping + print of src/neighborJoining.cu:233-270), iterative.  labels (optional, N-2
+// Newick text of an NJ merge log (../csrc/merge_log.hpp; bookkeeping + print of src/neighborJoining.cu:233-270), iterative.  labels (optional, N-2
 // entries): (*labels)[k] >= 0 is written after the `)` of internal node N+k (bootstrap support); without labels the text is
 // the reference's.
 void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
@@ -332,8 +332,8 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
 void writeNewickFromKids(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& kid, int32_t top,
                          const std::vector<double>& len);
 
-// Rooted Newick text `(A:l,B:l);` of a UPGMA / WPGMA log (dpr_upgma_run: N-1 merges with the realID bookkeeping of the NJ log, the
-// last one the root; h the height of every new node): a child's branch is its parent's height minus its own, as it comes.
+// Rooted Newick text `(A:l,B:l);` of a UPGMA / WPGMA log (dpr_upgma_run: N-1 merges over the slots of the NJ log, ../csrc/merge_log.hpp,
+// the last one the root; h the height of every new node): a child's branch is its parent's height minus its own, as it comes.
 // labels as writeNewickFromMerges (internal nodes N+k, k < N-2; the root carries none).
 void writeNewickFromUpgma(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
                           const std::vector<int32_t>& my, const std::vector<double>& h, const std::vector<int32_t>* labels = nullptr);

@@ -1,5 +1,6 @@
 // Readers and writers of the dipper host side.
 #include "dipper_host.hpp"
+#include "../csrc/merge_log.hpp"
 
 #include <fcntl.h>
 #include <sched.h>
@@ -671,21 +672,10 @@ void writeNewickFromMerges(std::ostream& os, const std::vector<std::string>& nam
                            const std::vector<double>& by, double last_d, const std::vector<int32_t>* labels)
 {
     const int N = (int)name.size();
-    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });  // two children per internal node
-    std::vector<int> realID((size_t)N);
-    for (int i = 0; i < N; ++i) realID[(size_t)i] = i;
-    int ID = N;
-    for (int it = 0; it < N - 2; ++it) {
-        const int x = mx[(size_t)it], y = my[(size_t)it];
-        kids[(size_t)ID * 2] = Child{ realID[(size_t)x], bx[(size_t)it] };
-        kids[(size_t)ID * 2 + 1] = Child{ realID[(size_t)y], by[(size_t)it] };
-        realID[(size_t)x] = ID++;
-        realID[(size_t)y] = realID[(size_t)(N - it - 1)];
-    }
-    const int root = 2 * N - 2;
-    kids[(size_t)root * 2] = Child{ realID[0], last_d * 0.5 };
-    kids[(size_t)root * 2 + 1] = Child{ realID[1], last_d * 0.5 };
-    writeBinaryNewick(os, name, kids, root, labels);
+    std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });  // two children per internal node, the x child first
+    auto edge = [&](int32_t parent, int side, int32_t child, double len) { kids[(size_t)parent * 2 + (size_t)side] = Child{ child, len }; };
+    if (!merge_log::nj_edges<false>(N, mx.data(), my.data(), bx.data(), by.data(), last_d, edge)) die("ERROR: internal: the merge log names a slot that is not live");
+    writeBinaryNewick(os, name, kids, 2 * N - 2, labels);
 }
 
 void writeNewickFromUpgma(std::ostream& os, const std::vector<std::string>& name, const std::vector<int32_t>& mx,
@@ -693,17 +683,8 @@ void writeNewickFromUpgma(std::ostream& os, const std::vector<std::string>& name
 {
     const int N = (int)name.size();
     std::vector<Child> kids((size_t)(2 * N) * 2, Child{ -1, 0.0 });
-    std::vector<int> realID((size_t)N);
-    std::vector<double> height((size_t)N, 0.0);
-    for (int i = 0; i < N; ++i) realID[(size_t)i] = i;
-    for (int it = 0; it < N - 1; ++it) {      // merge it makes node N + it; the last one, 2N - 2, is the root
-        const int x = mx[(size_t)it], y = my[(size_t)it], last = N - it - 1;
-        const double hnew = h[(size_t)it];
-        kids[(size_t)(N + it) * 2] = Child{ realID[(size_t)x], hnew - height[(size_t)x] };
-        kids[(size_t)(N + it) * 2 + 1] = Child{ realID[(size_t)y], hnew - height[(size_t)y] };
-        realID[(size_t)x] = N + it; height[(size_t)x] = hnew;
-        realID[(size_t)y] = realID[(size_t)last]; height[(size_t)y] = height[(size_t)last];
-    }
+    auto edge = [&](int32_t parent, int side, int32_t child, double len) { kids[(size_t)parent * 2 + (size_t)side] = Child{ child, len }; };
+    if (!merge_log::upgma_edges<false>(N, mx.data(), my.data(), h.data(), edge)) die("ERROR: internal: the merge log names a slot that is not live");
     writeBinaryNewick(os, name, kids, 2 * N - 2, labels);
 }
 

@@ -14,6 +14,7 @@
 // --upgma / --wpgma (one rank): dpr_upgma_run in place of every dpr_nj_run; the first n - 2 entries of its log are a merge log of the
 // same unrooted tree and go to the support functions unchanged, the whole log to writeNewickFromUpgma (the root carries no label).
 #include "dipper_host.hpp"
+#include "../csrc/merge_log.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -22,19 +23,12 @@
 
 namespace dipper {
 
-// clade sizes with the realID bookkeeping of writeNewickFromMerges
-static std::vector<int64_t> cladeSizes(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my)
+// clade sizes, children and root pair of a log of dpr_nj_run / dpr_upgma_run (../csrc/merge_log.hpp)
+static merge_log::Sizes cladeSizes(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my)
 {
-    std::vector<int64_t> size((size_t)(2 * n - 2), 1);
-    std::vector<int32_t> real((size_t)n);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int32_t x = mx[(size_t)it], y = my[(size_t)it];
-        size[(size_t)(n + it)] = size[(size_t)real[(size_t)x]] + size[(size_t)real[(size_t)y]];
-        real[(size_t)x] = (int32_t)(n + it);
-        real[(size_t)y] = real[(size_t)(n - it - 1)];
-    }
-    return size;
+    merge_log::Sizes s;
+    if (!merge_log::sizes_of<false>(n, mx.data(), my.data(), s)) die("ERROR: internal: the merge log names a slot that is not live");
+    return s;
 }
 
 std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my,
@@ -42,9 +36,9 @@ std::vector<int32_t> supportLabels(int64_t n, const std::vector<int32_t>& mx, co
 {
     std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
     if (n <= 3 || replicates <= 0) return labels;
-    const std::vector<int64_t> size = cladeSizes(n, mx, my);
+    const merge_log::Sizes t = cladeSizes(n, mx, my);
     for (int64_t k = 0; k < n - 2; ++k) {
-        const int64_t s = size[(size_t)(n + k)];
+        const int64_t s = t.size[(size_t)(n + k)];
         if (s >= 2 && s <= n - 2) labels[(size_t)k] = (int32_t)((200 * (int64_t)counts[(size_t)k] + replicates) / (2 * replicates));
     }
     return labels;
@@ -55,9 +49,9 @@ std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, c
 {
     std::vector<int32_t> labels((size_t)std::max<int64_t>(n - 2, 1), -1);
     if (n <= 3 || replicates <= 0) return labels;
-    const std::vector<int64_t> size = cladeSizes(n, mx, my);
+    const merge_log::Sizes t = cladeSizes(n, mx, my);
     for (int64_t k = 0; k < n - 2; ++k) {
-        const int64_t p = std::min(size[(size_t)(n + k)], n - size[(size_t)(n + k)]);
+        const int64_t p = std::min<int64_t>(t.size[(size_t)(n + k)], n - t.size[(size_t)(n + k)]);
         if (p < 2) continue;
         const int64_t den = replicates * (p - 1), num = den - phi_sum[(size_t)k];
         labels[(size_t)k] = (int32_t)((200 * num + den) / (2 * den));
@@ -69,38 +63,30 @@ std::vector<int32_t> transferLabels(int64_t n, const std::vector<int32_t>& mx, c
 static int64_t taxaBranches(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my)
 {
     if (n <= 3) return 0;
-    const std::vector<int64_t> size = cladeSizes(n, mx, my);
+    const merge_log::Sizes t = cladeSizes(n, mx, my);
+    auto p = [&](int64_t v) { return std::min<int64_t>(t.size[(size_t)v], n - t.size[(size_t)v]); };
     int64_t b = 0;
-    for (int64_t k = 0; k < n - 2; ++k) b += std::min(size[(size_t)(n + k)], n - size[(size_t)(n + k)]) >= 2;
+    for (int64_t k = 0; k < n - 2; ++k) b += p(n + k) >= 2;
     // (the root joins two complementary clades: both are branches exactly when both are internal nodes with p >= 2)
-    std::vector<int32_t> real((size_t)n);
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        real[(size_t)mx[(size_t)it]] = (int32_t)(n + it);
-        real[(size_t)my[(size_t)it]] = real[(size_t)(n - it - 1)];
-    }
-    if (real[0] >= n && real[1] >= n && std::min(size[(size_t)real[0]], n - size[(size_t)real[0]]) >= 2) --b;
+    if (t.root[0] >= n && t.root[1] >= n && p(t.root[0]) >= 2) --b;
     return b;
 }
 
 // The merge log of the same tree with tip `slot` renamed tipOf[slot]: the k-th merge joins the same two nodes into node n+k, so
-// per-node results keep their index; only the slots (the bookkeeping of writeNewickFromMerges, run for the new names) differ.
+// per-node results keep their index; only the slots (`at`, the slot map of the log being written, for the new names) differ.
 static void relabelledLog(int64_t n, const std::vector<int32_t>& mx, const std::vector<int32_t>& my, const std::vector<int32_t>& tipOf,
                           std::vector<int32_t>& ox, std::vector<int32_t>& oy)
 {
-    std::vector<int32_t> real((size_t)n), at((size_t)n), slot_of((size_t)std::max<int64_t>(2 * n - 2, n));
-    for (int64_t i = 0; i < n; ++i) real[(size_t)i] = at[(size_t)i] = slot_of[(size_t)i] = (int32_t)i;
-    for (int64_t it = 0; it < n - 2; ++it) {
-        const int32_t x = mx[(size_t)it], y = my[(size_t)it], last = (int32_t)(n - it - 1), v = (int32_t)(n + it);
-        const int32_t a = real[(size_t)x], b = real[(size_t)y];
+    std::vector<int32_t> real, at((size_t)n), slot_of((size_t)std::max<int64_t>(2 * n - 2, n));
+    for (int64_t i = 0; i < n; ++i) at[(size_t)i] = slot_of[(size_t)i] = (int32_t)i;
+    const bool ok = merge_log::replay<false>(n, n - 2, mx.data(), my.data(), real, [&](int64_t it, int32_t v, int32_t a, int32_t b) {
         const int32_t sa = slot_of[(size_t)(a < n ? tipOf[(size_t)a] : a)], sb = slot_of[(size_t)(b < n ? tipOf[(size_t)b] : b)];
         const int32_t lo = std::min(sa, sb), hi = std::max(sa, sb);
         ox[(size_t)it] = lo; oy[(size_t)it] = hi;
-        at[(size_t)lo] = v; slot_of[(size_t)v] = lo;
-        if (hi != last) { at[(size_t)hi] = at[(size_t)last]; slot_of[(size_t)at[(size_t)hi]] = hi; }
-        real[(size_t)x] = v;
-        real[(size_t)y] = real[(size_t)last];
-    }
+        merge_log::join_slots(at.data(), lo, hi, n - it, v);
+        slot_of[(size_t)v] = lo; slot_of[(size_t)at[(size_t)hi]] = hi;      // (hi the last live slot: nothing moved)
+    });
+    if (!ok) die("ERROR: internal: the merge log names a slot that is not live");
 }
 
 // moved / pairs to six decimals, rounded half up, from integers only
