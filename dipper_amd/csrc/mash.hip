@@ -201,8 +201,9 @@ __global__ __launch_bounds__(kThreads) void mash_dist_rows_kernel(const uint64_t
 // table on the leading 9 significant bits: base[bucket] = number of values in lower buckets, and
 // 8 x 15-bit tags per bucket (the next 15 bits of each value, ascending, in 16-bit fields).  One
 // 16-byte read of the bucket of an A value gives rank_B(v) = base + #(tags below v's tag); the
-// sketch entry at that rank decides the match (64-bit compare; equal tags of different values and
-// duplicates are walked, buckets with more than 8 values are flagged and binary-searched -- all rare).
+// sketch entry at that rank decides the match (64-bit compare at a rank below S -- the two pad entries
+// behind the sketch only end the walk; equal tags of different values and duplicates are walked, buckets
+// with more than 8 values are flagged and binary-searched -- all rare).
 // A wave holds one column sketch (the A list) in registers, strided: step u covers the 64 consecutive
 // values a[64u .. 64u+63], so (i) the lanes of one LDS instruction read ~33 consecutive buckets and
 // ~64 consecutive sketch entries (near conflict-free, unlike random probing, which is what bounds a
@@ -386,7 +387,9 @@ __global__ __launch_bounds__(kLThreads) void mash_dist_lookup_kernel(const uint6
                 if (__any(b0 < av)) {                            // equal tags of different values (rare)
                     while (b0 < av) b0 = v[++rankb];
                 }
-                const bool match = ((firstmask >> u) & 1u) && b0 == av;
+                // rankb < S: the two pad entries behind the row are no values of B -- the first ~0 of a padded A would meet
+                // them at rank S, and with duplicates in B (mtotal can exceed pos) pass the cut-off below
+                const bool match = ((firstmask >> u) & 1u) && rankb < S && b0 == av;
                 const unsigned long long mb = __ballot(match);
                 int madd;
                 if (row_dups) {                                  // multiplicities in B: full prefix sum
