@@ -133,18 +133,18 @@ void startRanks(const RankOptions& o, int base_device);
 // rank 0's closing line of a multi-rank run: "Ranks: G (transport, N device collectives; NJ plan ...)"; nothing with one rank
 void printRankSummary(dpr_ctx* ctx);
 
-// --bionj: every context this command creates builds BIONJ trees (dpr_ctx_set_nj_variant); set by main() before the first one
+// --bionj: every context this command creates builds BIONJ trees (dpr_ctx_set_nj_variant); set by applyOptions (options.cpp) before the first one
 bool& bionjOption();
 // --upgma (0) / --wpgma (1): the linkage every tree of this command is clustered with (dpr_upgma_run in place of dpr_nj_run);
-// -1 = NJ.  Set by main() before the first tree
+// -1 = NJ.  Set by applyOptions before the first tree
 int& upgmaOption();
 
 // --fit [--fit-taxa FILE]: after the tree is written, the fit of that tree to a FRESH distance matrix (dpr_tree_fit): one `Fit:` line
-// and the five worst taxa on stderr, the per-taxon table to FILE.  Set by main() before the first tree.
+// and the five worst taxa on stderr, the per-taxon table to FILE.  Set by applyOptions before the first tree.
 struct FitOption {
     bool on = false;
     std::string taxaFile;                // --fit-taxa, or empty
-    std::ofstream* taxa = nullptr;       // that file, opened by main() before the tree is built
+    std::ofstream* taxa = nullptr;       // that file, opened by the runner (main.cpp) before the tree is built
     std::vector<int> slotOfInput;        // slot of the taxon read i-th (the table lists the taxa in input order); empty: slot = input order
 };
 struct DeviceContext;
@@ -154,7 +154,7 @@ void reportFit(DeviceContext& dev, const std::vector<std::string>& name, const s
 
 // --site-coverage X / --complete-deletion (-i m): every alignment this command uploads -- the three MSADeviceArrays uploads and the
 // bootstrap's rank-local context -- keeps only the columns in which at least X of the sequences hold a symbol
-// (dpr_msa_filter_sites).  Set by main() before the first upload.
+// (dpr_msa_filter_sites).  Set by applyOptions before the first upload.
 struct SiteFilterOption {
     int permille = 0;            // X in per mille, 0 = off
     std::string text;            // X in canonical form: "1", "0.5", "0.667"
@@ -247,6 +247,8 @@ struct Tree {
     Tree(const std::string& newick, size_t totalLeaves);
     int findLeaf(const std::string& name) const;   // node index or -1
 };
+// --add: for every record name the idx of the leaf of t that carries it, -1 where the tree has no such leaf (a query)
+std::vector<int> leafIndexByName(const Tree& t, const std::vector<std::string>& names);
 
 struct BootstrapOptions;
 // one row of a query's jplace record: the backbone edge (edge k = the k-th non-root node in post-order of the -t file), the

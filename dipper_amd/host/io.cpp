@@ -572,6 +572,41 @@ std::vector<int> shuffledIds(size_t n, long long seed)
     return ids;
 }
 
+std::vector<int> leafIndexByName(const Tree& t, const std::vector<std::string>& names)
+{
+    // name -> leaf index: an open-addressing table over the tree's own names (later duplicates win, as with a map), filled
+    // serially, then looked up by all host threads -- a node-based map cost 140 ms for 500 000 tips + 550 000 records
+    auto hash_of = [](const std::string& v) {
+        uint64_t h = 1469598103934665603ull;
+        for (unsigned char ch : v) { h ^= ch; h *= 1099511628211ull; }
+        return h ^ (h >> 29);
+    };
+    size_t cap = 16;
+    while (cap < 2 * t.nodes.size()) cap <<= 1;
+    std::vector<int32_t> table(cap, -1);
+    for (size_t k = 0; k < t.nodes.size(); ++k) {          // (the table holds positions in t.nodes)
+        const Node& nd = t.nodes[k];
+        if (!nd.children.empty()) continue;
+        size_t h = (size_t)hash_of(nd.name) & (cap - 1);
+        while (table[h] >= 0 && t.nodes[(size_t)table[h]].name != nd.name) h = (h + 1) & (cap - 1);
+        table[h] = (int32_t)k;
+    }
+    const size_t n = names.size();
+    std::vector<int> ids(n);
+    const unsigned nt = hostThreads(32);
+    std::vector<std::thread> pool;
+    for (unsigned w = 0; w < nt; ++w)
+        pool.emplace_back([&, w] {
+            for (size_t i = n * w / nt; i < n * (w + 1) / nt; ++i) {
+                size_t h = (size_t)hash_of(names[i]) & (cap - 1);
+                while (table[h] >= 0 && t.nodes[(size_t)table[h]].name != names[i]) h = (h + 1) & (cap - 1);
+                ids[i] = table[h] >= 0 ? t.nodes[(size_t)table[h]].idx : -1;
+            }
+        });
+    for (std::thread& th : pool) th.join();
+    return ids;
+}
+
 void MatrixReader::read(const std::string& path)
 {
     FILE* fp = std::fopen(path.c_str(), "r");
