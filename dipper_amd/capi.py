@@ -192,6 +192,14 @@ def load_library():
     L.dpr_transfer_taxa_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i64p, c_i64p, c_i64p]
     L.dpr_ctx_set_tbe_lds.argtypes = [C.c_void_p, C.c_int64]
     L.dpr_comm_sum_i64.argtypes = [C.c_void_p, c_i64p, C.c_int64]
+    L.dpr_pairs_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int64]
+    L.dpr_pairs_next.argtypes = [C.c_void_p, C.POINTER(c_i32p), C.POINTER(c_i32p), C.POINTER(c_f64p), c_i64p, c_i64p]
+    L.dpr_pairs_labels.argtypes = [C.c_void_p, c_i32p]
+    L.dpr_pairs_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_pairs_end.argtypes = [C.c_void_p]
+    L.dpr_get_pairs_info.argtypes = [C.c_void_p, c_f64p, c_i64p]
+    L.dpr_pairs_within_host.argtypes = [c_f64p, C.c_int64, C.c_double, c_i32p, c_i32p, c_f64p, C.c_int64, c_i64p, c_i32p]
+    L.dpr_pairs_summary_host.argtypes = [c_i32p, C.c_int64, c_i64p, c_i32p]
     _LIB = L
     return L
 
@@ -489,6 +497,37 @@ def upgma_host(D, linkage=0):
     mx, my, h = np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.float64)
     _chk(lib, lib.dpr_upgma_host(_p(rows, c_f64p), n, int(linkage), _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p)))
     return dict(merge_x=mx[: n - 1], merge_y=my[: n - 1], height=h[: n - 1])
+
+
+PAIRS_STATS = ("blocks", "pairs", "components", "largest", "singletons", "peak_device_bytes")
+
+
+def pairs_summary_host(label):
+    """what the labels of pairs_within say (host only): dict(components, largest, singletons, rank) -- rank[v] the 1-based rank of v's
+    cluster, clusters ordered by their smallest member"""
+    lib = load_library()
+    label = np.ascontiguousarray(label, dtype=np.int32)
+    out, rank = np.zeros(3, dtype=np.int64), np.zeros(len(label), dtype=np.int32)
+    _chk(lib, lib.dpr_pairs_summary_host(_p(label, c_i32p), len(label), _p(out, c_i64p), _p(rank, c_i32p)))
+    return dict(components=int(out[0]), largest=int(out[1]), singletons=int(out[2]), rank=rank)
+
+
+def pairs_within_host(D, threshold):
+    """The pairs j < i of the strict lower triangle of the (n, n) array D with D[i, j] <= threshold, ordered by i then j, and
+    label[v] = the smallest index of v's connected component, restated on the host (no GPU): dict(i, j, d, label, stats) as
+    Dipper.pairs_within returns them (stats without blocks and peak_device_bytes)"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    count = C.c_int64(0)
+    _chk(lib, lib.dpr_pairs_within_host(_p(rows, c_f64p), n, float(threshold), None, None, None, 0, C.byref(count), None))
+    cap = max(count.value, 1)
+    i, j, d, label = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(n, dtype=np.int32)
+    _chk(lib, lib.dpr_pairs_within_host(_p(rows, c_f64p), n, float(threshold), _p(i, c_i32p), _p(j, c_i32p), _p(d, c_f64p), cap, C.byref(count),
+                                        _p(label, c_i32p)))
+    k = count.value
+    s = pairs_summary_host(label)
+    return dict(i=i[:k], j=j[:k], d=d[:k], label=label,
+                stats=dict(pairs=k, components=s["components"], largest=s["largest"], singletons=s["singletons"]))
 
 
 FIT_SUMS = ("n", "skipped", "sum_d", "sum_p", "sum_dd", "sum_pp", "sum_dp", "ss", "wss", "n_w", "max_e", "rms", "rms_rel", "explained",
@@ -1139,6 +1178,59 @@ class Dipper:
         a = C.c_double()
         _chk(self.L, self.L.dpr_get_upgma_timing(self.h, C.byref(a)))
         return a.value
+
+    def pairs_begin(self, source, dist_type=1, k=15, threshold=0.0, block_rows=0):
+        _chk(self.L, self.L.dpr_pairs_begin(self.h, source, dist_type, k, float(threshold), int(block_rows)))
+
+    def pairs_next(self, copy=True):
+        """(i, j, d, rows_done) of the next row block: copies of the library's pinned arrays (copy=False: views, valid until the next call)"""
+        pi, pj, pd = c_i32p(), c_i32p(), c_f64p()
+        cnt, done = C.c_int64(0), C.c_int64(0)
+        _chk(self.L, self.L.dpr_pairs_next(self.h, C.byref(pi), C.byref(pj), C.byref(pd), C.byref(cnt), C.byref(done)))
+        k = cnt.value
+        if k == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0), done.value
+        out = [np.ctypeslib.as_array(p, (k,)) for p in (pi, pj, pd)]
+        return (*[a.copy() if copy else a for a in out], done.value)
+
+    def pairs_labels(self, n):
+        label = np.zeros(n, dtype=np.int32)
+        _chk(self.L, self.L.dpr_pairs_labels(self.h, _p(label, c_i32p)))
+        return label
+
+    def pairs_stats(self):
+        out = np.zeros(6, dtype=np.int64)
+        _chk(self.L, self.L.dpr_pairs_stats(self.h, _p(out, c_i64p)))
+        return {k: int(out[t]) for t, k in enumerate(PAIRS_STATS)}
+
+    def pairs_info(self):
+        """dict(dist_ms, filter_ms, copy_ms, block_rows, n) of the stream so far (ms: HIP events, summed over its blocks)"""
+        ms, shape = np.zeros(3), np.zeros(2, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_pairs_info(self.h, _p(ms, c_f64p), _p(shape, c_i64p)))
+        return dict(dist_ms=float(ms[0]), filter_ms=float(ms[1]), copy_ms=float(ms[2]), block_rows=int(shape[0]), n=int(shape[1]))
+
+    def pairs_end(self):
+        _chk(self.L, self.L.dpr_pairs_end(self.h))
+
+    def pairs_within(self, source, dist_type=1, k=15, threshold=0.0, block_rows=0, keep=True):
+        """The pairs j < i within `threshold` of the uploaded source (alignment, sketches, or the matrix of set_matrix_lower), ordered
+        by i then j, streamed in blocks of block_rows rows (0: the library's choice) without ever building the matrix, and the
+        single-linkage clusters they form: dict(i, j, d, label, stats, info).  label[v] is the smallest index of v's cluster; stats
+        has the keys of PAIRS_STATS, info those of pairs_info.  keep=False: the pairs are counted and dropped (measurement runs)"""
+        self.pairs_begin(source, dist_type, k, threshold, block_rows)
+        try:
+            n = self.pairs_info()["n"]
+            parts, done = [], 0
+            while done < n:
+                pi, pj, pd, done = self.pairs_next(copy=keep)
+                if len(pi) and keep:
+                    parts.append((pi, pj, pd))
+            label = self.pairs_labels(n)
+            stats, info = self.pairs_stats(), self.pairs_info()
+        finally:
+            self.pairs_end()
+        cat = (lambda t, dt: np.concatenate([p[t] for p in parts]) if parts else np.zeros(0, dtype=dt))
+        return dict(i=cat(0, np.int32), j=cat(1, np.int32), d=cat(2, np.float64), label=label, stats=stats, info=info)
 
     def tree_fit(self, parent, length, n=None):
         """tree_fit_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run); the

@@ -182,6 +182,7 @@ int dpr_destroy(dpr_ctx* c)
     exact_free(c->exact);
     pfix_free(c->pfix);
     tbe_free(c->tbe);
+    c->pairs.reset();
     if (c->place_trace) (void)hipFree(c->place_trace);
     if (c->packed_lower) (void)hipFree(c->packed_lower);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -64,6 +65,7 @@ struct dpr_ctx {
     dpr::BmeBuffers bme;             // dpr_bme_nni: the table of subtree averages and its small arrays
     dpr::UpgmaBuffers upgma;         // dpr_upgma_run: the working copy of the matrix, the nearest-neighbour cache and the log
     dpr::FitBuffers fit;             // dpr_tree_fit: the tree's lookup tables and the per-taxon parts
+    std::unique_ptr<dpr::PairsBuffers> pairs;    // dpr_pairs_begin .. dpr_pairs_end: the stream in progress, else empty
     int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip
     double* packed_lower = nullptr;  // MATRIX source, device

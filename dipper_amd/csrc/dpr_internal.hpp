@@ -509,6 +509,38 @@ struct FitBuffers {
     int compare = 0;                     // dpr_ctx_set_fit_compare: time the NJ row-sum kernel beside the passes
 };
 
+// ---- pairs within a threshold and their components (pairs.hip; driver in ctx_pairs.hip) --------------------------------------------
+// Everything lives from dpr_pairs_begin to dpr_pairs_end (or the next begin, or dpr_destroy); nothing of the context's other state is
+// touched.  Device memory: the row block, the pair buffers (grown to the largest block met, at most block_rows * n entries), O(n) for
+// the parents and O(block_rows) for the counts.
+using PinnedBuf = HipOwner<void*, hipHostFree>;
+constexpr int kPairsThreads = 256;                       // one workgroup walks one row
+constexpr int kPairsChunk = 2 * kPairsThreads;           // columns per step of the walk: two per lane, kPairsThreads apart
+constexpr int64_t kPairsBlockBytes = (int64_t)1 << 30;   // block_rows 0: the row block takes at most this much
+constexpr int64_t kPairsMaxRows = 32768;                 // rows of one block, whatever was asked for (the whole matrix is built in such blocks too)
+struct PairsBuffers {
+    bool ended = false, labelled = false;
+    int source = 0, dist_type = 0;
+    double threshold = 0;
+    int64_t n = 0, block_rows = 0, ld = 0, next_row = 0;
+    DevBuf<double> block;                // [block_rows][ld] rows of the current block (MSA, Mash; the packed triangle is read in place)
+    DevBuf<int64_t> cnt;                 // [block_rows + 1] pairs kept per row, then their exclusive scan in place; [nr] the block's total
+    DevBuf<int32_t> pi, pj;              // [cap] the block's pairs, ordered
+    DevBuf<double> pd;
+    DevBuf<int32_t> parent;              // [n] union-find forest: parent[v] <= v
+    int64_t cap = 0;
+    PinnedBuf hi, hj, hd, htotal;        // host side of pi / pj / pd (cap entries each) and of the block's total
+    int64_t dev_bytes = 0, peak_bytes = 0;
+    int64_t blocks = 0, pairs = 0, comps = 0, largest = 0, singletons = 0;
+    double dist_ms = 0, filter_ms = 0, copy_ms = 0;      // summed over the blocks (HIP events): the provider; count + scan + write + hook; the copies back
+};
+// rows [r0, r0 + nr): row i's entries j < i are rows[(i - r0) * ld + j], or -- packed -- rows[i (i - 1) / 2 + j] (rows = the triangle)
+int pairs_count_scan(const double* rows, int64_t ld, bool packed, int64_t r0, int64_t nr, double threshold, int64_t* cnt, hipStream_t s);   // cnt[t] = first pair of row r0 + t, cnt[nr] = total
+int pairs_write_hook(const double* rows, int64_t ld, bool packed, int64_t r0, int64_t nr, double threshold, const int64_t* cnt, int64_t total,
+                     int32_t* pi, int32_t* pj, double* pd, int32_t* parent, int64_t n, hipStream_t s);
+int pairs_parent_init(int32_t* parent, int64_t n, hipStream_t s);
+int pairs_flatten(const int32_t* parent, int32_t* out, int64_t n, hipStream_t s);      // out[v] = root of v (out may be parent itself)
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of kIC = 1 024 tips the (value -> tips, positions) postings
 struct MashIndex {

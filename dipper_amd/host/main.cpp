@@ -227,6 +227,88 @@ int runDistanceOutput(const Options& o)
     return 0;
 }
 
+// -o p --within T [--clusters FILE]: the pairs of sequences whose distance is <= T and the single-linkage clusters they form, from any
+// of the three inputs.  The sequences go to the device as runDistanceOutput sends them (input order), so a distance here is the number
+// -o d prints; the matrix itself is never built: the library streams blocks of rows and returns each block's pairs in (i, j) order
+// (dpr_pairs_begin / _next), and joins them into components on the device (dpr_pairs_labels).
+int runPairsOutput(const Options& o)
+{
+    Param params = o.params;
+    std::vector<std::string> seqs, names_, names;
+    MatrixReader matrixReader;
+    if (params.in == "d") {
+        matrixReader.read(o.inputFile);
+        names = matrixReader.name;
+    } else {
+        readSequences(o.inputFile, seqs, names_);
+        names = names_;      // (input order: shuffledIds(n, -1) is the identity)
+    }
+    const size_t n = names.size();
+    if (n < 2) die("ERROR: need at least two sequences in " + o.inputFile);
+    const std::vector<int> ids = shuffledIds(n, -1);
+    // the report first: a path that cannot be written ends the run without a pair file
+    std::unique_ptr<std::ofstream> clusters_;
+    if (!o.clustersFile.empty()) clusters_ = openFile(o.clustersFile, "the --clusters file");
+    auto output_ = openFile(o.outputFile, "output file");
+    DeviceContext dev(o.device);
+    MSADeviceArrays msaDeviceArrays;
+    MashDeviceArrays mashDeviceArrays;
+    int source = DPR_SRC_MATRIX;
+    if (params.in == "d") {
+        gpuCheck(dpr_set_matrix_lower(dev.ctx, matrixReader.lower.data(), (int64_t)n), "dpr_set_matrix_lower");
+    } else {
+        const bool aligned = params.in == "m";
+        source = aligned ? DPR_SRC_MSA : DPR_SRC_MASH;
+        allocateSequences(dev, aligned, o.protein, PackedSequences(), false, seqs, ids, msaDeviceArrays, mashDeviceArrays);
+        if (!aligned) mashDeviceArrays.sketchConstructionOnGpu(dev, params);
+    }
+    gpuCheck(dpr_pairs_begin(dev.ctx, source, (int)params.distanceType, (int)params.kmerSize, o.within, 0), "dpr_pairs_begin");
+    *output_ << "ID1\tID2\tDistance\n";
+    std::string text;
+    char buf[64];
+    int64_t done = 0, kept = 0;
+    while (done < (int64_t)n) {
+        const int32_t *pi = nullptr, *pj = nullptr;
+        const double* pd = nullptr;
+        int64_t count = 0;
+        gpuCheck(dpr_pairs_next(dev.ctx, &pi, &pj, &pd, &count, &done), "dpr_pairs_next");
+        text.clear();
+        for (int64_t k = 0; k < count; ++k) {
+            text += names[(size_t)pi[k]];
+            text += '\t';
+            text += names[(size_t)pj[k]];
+            std::snprintf(buf, sizeof(buf), "\t%.9g\n", pd[k]);
+            text += buf;
+        }
+        output_->write(text.data(), (std::streamsize)text.size());
+        kept += count;
+    }
+    std::vector<int32_t> label(n), rank(n);
+    gpuCheck(dpr_pairs_labels(dev.ctx, label.data()), "dpr_pairs_labels");
+    int64_t sum[3] = { 0, 0, 0 }, stats[6] = { 0, 0, 0, 0, 0, 0 };
+    gpuCheck(dpr_pairs_summary_host(label.data(), (int64_t)n, sum, rank.data()), "dpr_pairs_summary_host");
+    gpuCheck(dpr_pairs_stats(dev.ctx, stats), "dpr_pairs_stats");
+    if (cliLog()) {
+        double ms[3] = { 0, 0, 0 };
+        int64_t shape[2] = { 0, 0 };
+        dpr_get_pairs_info(dev.ctx, ms, shape);
+        std::cerr << "  device: " << stats[0] << " blocks of " << shape[0] << " rows; distances " << ms[0] << " ms, filter and components " << ms[1]
+                  << " ms, copies " << ms[2] << " ms; peak device bytes " << stats[5] << "\n";
+    }
+    gpuCheck(dpr_pairs_end(dev.ctx), "dpr_pairs_end");
+    output_->flush();
+    if (!*output_) die("ERROR: cannot write output file: " + o.outputFile);
+    const std::string tail = std::to_string(sum[0]) + " clusters, largest " + std::to_string(sum[1]) + ", " + std::to_string(sum[2]) + " singletons";
+    if (clusters_) {
+        *clusters_ << "# " << n << " sequences, " << kept << " pairs within " << o.withinText << ", " << tail << "\n";
+        for (size_t v = 0; v < n; ++v) *clusters_ << names[v] << "\t" << rank[v] << "\n";
+        clusters_->flush();
+        if (!*clusters_) die("ERROR: cannot write the --clusters file: " + o.clustersFile);
+    }
+    std::cerr << "Pairs: " << kept << " of " << (long long)n * ((long long)n - 1) / 2 << " within " << o.withinText << " (" << tail << ")\n";
+    return 0;
+}
+
 // -i m / -i r -o t: the tree of the sequences, in the mode their number selects.  This is the timed path: the order of its steps is kept
 int runFromSequences(const Options& o, Clock::time_point inputStart)
 {
@@ -408,6 +490,7 @@ int main(int argc, char** argv)
     const bool sequences = o.params.in == "m" || o.params.in == "r";
     if (o.add) return runAdd(o, inputStart);
     if (sequences && o.params.out == "d") return runDistanceOutput(o);
+    if (o.pairs && (sequences || o.params.in == "d")) return runPairsOutput(o);
     if (sequences && o.params.out == "t") return runFromSequences(o, inputStart);
     if (o.params.in == "d" && o.params.out == "t") return runFromMatrix(o);
     std::printf("Invalid input-output combinations!!!!!\n");

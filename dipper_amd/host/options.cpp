@@ -27,6 +27,8 @@ const char* const kHelp =
     "                                j - placements in jplace format: every query placed on the\n"
     "                                    backbone by itself, the backbone unchanged (needs --add -t,\n"
     "                                    -i m or -i r; with --bootstrap: placement support per edge)\n"
+    "                                p - the pairs of sequences within a distance threshold (needs --within;\n"
+    "                                    -i m, r or d), as a table; no tree and no matrix is built\n"
     "  -m [ --algorithm ] arg      Algorithm selection:\n"
     "                                0 - default mode\n"
     "                                1 - force placement\n"
@@ -125,6 +127,20 @@ const char* const kHelp =
     "                              in input order its counted pairs, residual sum of squares, rms residual and\n"
     "                              that rms over the tree-wide rms (tab-separated, 17 significant digits).\n"
     "                              Needs --fit\n"
+    "  --within arg                With -o p: the distance threshold T, a decimal >= 0.  The output file gets the\n"
+    "                              line `ID1<TAB>ID2<TAB>Distance`, then one line per pair of sequences whose\n"
+    "                              distance d -- the number -o d prints for the pair -- is <= T (a distance\n"
+    "                              that is not a number or infinite never is), ordered by the later sequence\n"
+    "                              of the pair in input order, then by the earlier one; input order is kept\n"
+    "                              (--seed, -m and -p are not consulted).  The distances are computed on the\n"
+    "                              GPU a block of rows at a time and filtered there: the matrix is never held,\n"
+    "                              so inputs far beyond the reach of -o d work.  One line `Pairs:` on stderr.\n"
+    "                              -i m with every -d, --protein, --site-coverage / --complete-deletion; -i r\n"
+    "                              with -k / -s; -i d; one GPU.  Not with --add, -t or a tree option\n"
+    "  --clusters arg              With -o p: write the single-linkage clusters at T -- the connected components\n"
+    "                              of the pairs -- to file arg: a `#` line with the totals, then every sequence\n"
+    "                              in input order with the number of its cluster (clusters numbered from 1 by\n"
+    "                              their first sequence).  Computed on the GPU\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -155,6 +171,7 @@ static const Opt kOpts[] = {
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
     { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
     { "site-coverage", 0, true }, { "complete-deletion", 0, false }, { "fit", 0, false }, { "fit-taxa", 0, true }, { "dump-newick", 0, true },
+    { "within", 0, true }, { "clusters", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -338,7 +355,7 @@ Options parseOptions(int argc, char** argv)
     auto treeBuilder = [&](const std::string& label, const char* wording, const char* noBootstrap, bool one_gpu) {
         if (o.algo == "1" || o.algo == "3") usageError(label + wording + " (-m 2, or the default mode below 30000 sequences)");
         if (o.add) usageError(label + " is not supported with --add");
-        if (params.out == "d" || params.out == "j") usageError(label + " needs tree output (-o t)");
+        if (params.out == "d" || params.out == "j" || params.out == "p") usageError(label + " needs tree output (-o t)");
         if (noBootstrap && has("bootstrap")) usageError(label + " is not supported with --bootstrap (" + noBootstrap + ")");
         if (o.njOnly.empty()) o.njOnly = label + wording;
         if (one_gpu) oneGpu.push_back(label);
@@ -401,6 +418,30 @@ Options parseOptions(int argc, char** argv)
         if (has("bootstrap") && params.in != "m") usageError("--bootstrap with -o j needs aligned sequences (-i m)");
         if (has("bootstrap-metric")) usageError("--bootstrap-metric does not apply to -o j (placement support is the share of replicates per edge)");
         if (has("bootstrap-taxa") || has("bootstrap-taxa-cutoff")) usageError("--bootstrap-taxa does not apply to -o j");
+    }
+    // -o p: the pairs within a threshold
+    o.pairs = params.out == "p";
+    if (has("within") && !o.pairs) usageError("--within needs the pair output (-o p)");
+    if (has("clusters") && !o.pairs) usageError("--clusters needs the pair output (-o p)");
+    if (o.pairs) {
+        if (!has("within")) usageError("-o p needs a distance threshold (--within T)");
+        // a finite decimal >= 0 that strtod consumes whole (no leading blank, no hexadecimal, no `inf` / `nan`)
+        o.withinText = vm.at("within");
+        const std::string& wv = o.withinText;
+        bool plain = !wv.empty() && wv.size() <= 64;
+        for (char ch : wv) plain = plain && (std::isdigit((unsigned char)ch) || ch == '.' || ch == 'e' || ch == 'E' || ch == '+' || ch == '-');
+        char* endp = nullptr;
+        o.within = plain ? std::strtod(wv.c_str(), &endp) : -1.0;
+        if (!plain || endp != wv.c_str() + wv.size() || !(o.within >= 0.0) || !std::isfinite(o.within))
+            usageError("--within: the threshold must be a finite decimal >= 0 (0.015)");
+        if (o.add || has("input-tree")) usageError("-o p is not supported with --add or -t (it compares the sequences of one input with each other)");
+        if (has("bootstrap")) usageError("--bootstrap needs tree output (-o t)");
+        if (has("clusters")) {
+            o.clustersFile = vm.at("clusters");
+            if (o.clustersFile.empty()) usageError("--clusters: a file name");
+            if (o.clustersFile == o.outputFile) usageError("--clusters: the file must differ from the output file (-O)");
+        }
+        oneGpu.push_back("-o p");
     }
     parseBootstrap(vm, o);
 

@@ -14,12 +14,15 @@ struct Options {
     Param params;
     BootstrapOptions boot;
     RankOptions ranks;
-    std::string inputFile, outputFile, treeFile, bootTaxaFile, fitTaxaFile;
+    std::string inputFile, outputFile, treeFile, bootTaxaFile, fitTaxaFile, clustersFile;
     std::string algo = "0";      // -m
     bool exact_mode = false, add = false, jplace = false, protein = false, bionj = false, spr = false, fit = false;
     int nni = -1;                // rounds of --nni / --spr, -1 = no refinement
     int upgma = -1;              // the linkage: 0 --upgma, 1 --wpgma, -1 = NJ
     int sitePermille = 0;        // --site-coverage / --complete-deletion, 0 = off
+    bool pairs = false;          // -o p: the pairs within --within and, with --clusters, the clusters they form
+    double within = 0;           // --within T, a finite number >= 0 ...
+    std::string withinText;      // ... and T as it was given (the reports name it so)
     std::string siteText;
     long long seed = 1;
     int device = 0;

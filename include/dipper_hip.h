@@ -815,6 +815,49 @@ int dpr_get_fit_stats(dpr_ctx *ctx, int64_t *out4);
 int dpr_get_fit_timing(dpr_ctx *ctx, double *row_ms, double *col_ms, double *rowsum_ms);
 int dpr_ctx_set_fit_compare(dpr_ctx *ctx, int on);
 
+/* ---- Pairs within a distance threshold and the clusters they form (the command's -o p; no reference counterpart) -------------------
+ * Contract.  Over the n tips of a source, with D_ij the entry dpr_dist_matrix would give the pair: the pairs are all (i, j), j < i,
+ *   with D_ij <= threshold compared in fp64 -- a NaN and +inf are never within it, -inf always is -- ordered by i, then by j; d is
+ *   D_ij bit for bit.  The clusters are the connected components of the graph these pairs span (single linkage at the threshold);
+ *   label[v] is the smallest tip index of v's component.  Nothing depends on a launch geometry, on block_rows or on the order in which
+ *   the device joins components.
+ * dpr_pairs_begin starts a stream over the uploaded alignment (DPR_SRC_MSA, dist_type as dpr_dist_matrix takes it), the sketches
+ *   (DPR_SRC_MASH, k the sketch k) or the triangle of dpr_set_matrix_lower (DPR_SRC_MATRIX); DPR_ERR_STATE without that input.  A
+ *   threshold that is NaN, infinite or negative, a negative block_rows, several ranks, virtual ranks: DPR_ERR_ARG.  A stream still open
+ *   on the context is dropped.  block_rows: rows of one block, at most 32 768 and n; 0 = as many as put the block at 1 GiB or less
+ *   (8 bytes x block_rows x n rounded up to 16 columns), in whole multiples of 64 rows.
+ * Memory.  The n x n matrix is never allocated.  The device holds one block of rows (none for DPR_SRC_MATRIX: the triangle the upload
+ *   left is read in place), the pairs of one block (16 bytes each; grown to the largest block met, never beyond block_rows (n - 1)
+ *   pairs), 8 (block_rows + 1) bytes of counts and 4 n bytes of parents (4 n more during dpr_pairs_labels): O(block_rows n) + O(n).
+ * State.  The context's inputs, its matrix and its NJ state are not touched: a dpr_dist_matrix + dpr_nj_run after a stream gives the
+ *   merge log a fresh context gives.
+ * dpr_pairs_next computes the next block: the provider's rows [r0, r0 + nr) x columns [0, r0 + nr), a count of the kept entries per
+ *   row, an exclusive scan, the ordered write, the union of the block's pairs into the forest.  *i, *j, *d point at *count entries in
+ *   pinned host memory the library owns, valid until the next call on the context's stream of pairs (NULL when *count is 0);
+ *   *rows_done = r0 + nr.  A block may hold no pair; *count == 0 with *rows_done == n is the end of the stream, and every later call
+ *   says the same.  DPR_ERR_STATE before dpr_pairs_begin.
+ * dpr_pairs_labels, once rows_done has reached n (DPR_ERR_STATE before): label[n].
+ * dpr_pairs_stats: out[0] blocks computed, 1 pairs delivered, and -- 0 until dpr_pairs_labels -- 2 components, 3 members of the
+ *   largest, 4 components of one member; 5 the largest number of bytes of device memory the stream held at any time.
+ * dpr_pairs_end releases everything the stream holds (also done by dpr_destroy); without a stream it does nothing. */
+int dpr_pairs_begin(dpr_ctx *ctx, int source, int dist_type, int k, double threshold, int64_t block_rows);
+int dpr_pairs_next(dpr_ctx *ctx, const int32_t **i, const int32_t **j, const double **d, int64_t *count, int64_t *rows_done);
+int dpr_pairs_labels(dpr_ctx *ctx, int32_t *label);
+int dpr_pairs_stats(dpr_ctx *ctx, int64_t out[6]);
+int dpr_pairs_end(dpr_ctx *ctx);
+/* of the stream so far (either may be NULL).  ms: summed over its blocks (HIP events) the row provider; count + scan + write +
+ * union; the copies of the pairs to the host.  shape: the rows of a block as dpr_pairs_begin settled them, and n. */
+int dpr_get_pairs_info(dpr_ctx *ctx, double ms[3], int64_t shape[2]);
+/* host only, no GPU: the contract restated as a double loop over the strict lower triangle (lower_rows, row by row, as
+ * dpr_set_matrix_lower takes it) and a union-find -- on purpose not the device's algorithm -- the reference of the GPU tests.  The
+ * first min(*count, cap) pairs go to i / j / d (which may be NULL when cap is 0), *count is the number found; label may be NULL.
+ * n < 2, a bad threshold, a null pointer: DPR_ERR_ARG. */
+int dpr_pairs_within_host(const double *lower_rows, int64_t n, double threshold, int32_t *i, int32_t *j, double *d, int64_t cap,
+                          int64_t *count, int32_t *label);
+/* host only: what labels say.  out3: components, members of the largest, components of one member; rank[n] (may be NULL): the 1-based
+ * rank of every tip's component, components ordered by their smallest member.  Labels that are not component minima: DPR_ERR_ARG. */
+int dpr_pairs_summary_host(const int32_t *label, int64_t n, int64_t out3[3], int32_t *rank);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
