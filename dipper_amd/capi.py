@@ -200,6 +200,12 @@ def load_library():
     L.dpr_get_pairs_info.argtypes = [C.c_void_p, c_f64p, c_i64p]
     L.dpr_pairs_within_host.argtypes = [c_f64p, C.c_int64, C.c_double, c_i32p, c_i32p, c_f64p, C.c_int64, c_i64p, c_i32p]
     L.dpr_pairs_summary_host.argtypes = [c_i32p, C.c_int64, c_i64p, c_i32p]
+    L.dpr_nearest_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
+    L.dpr_nearest_next.argtypes = [C.c_void_p, C.POINTER(c_i32p), C.POINTER(c_f64p), C.POINTER(c_i32p), c_i64p, c_i64p]
+    L.dpr_nearest_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_nearest_end.argtypes = [C.c_void_p]
+    L.dpr_get_nearest_info.argtypes = [C.c_void_p, c_f64p, c_i64p]
+    L.dpr_nearest_host.argtypes = [c_f64p, C.c_int64, C.c_int, c_i32p, c_f64p, c_i32p]
     _LIB = L
     return L
 
@@ -528,6 +534,23 @@ def pairs_within_host(D, threshold):
     s = pairs_summary_host(label)
     return dict(i=i[:k], j=j[:k], d=d[:k], label=label,
                 stats=dict(pairs=k, components=s["components"], largest=s["largest"], singletons=s["singletons"]))
+
+
+NEAREST_STATS = ("blocks", "neighbours", "fewer", "none", "flushes", "peak_device_bytes")
+NEAREST_MAX_K = 256
+
+
+def nearest_host(D, K):
+    """Each row's K nearest neighbours in the (n, n) array D, whose strict lower triangle is read as a symmetric matrix, restated on
+    the host (no GPU): dict(j [n, K] int32, d [n, K], cnt [n] int32) as Dipper.nearest returns them.  Row i holds the columns c != i
+    with a finite entry, by distance and then by column; behind the cnt[i] real places j is -1 and d the NaN 0x7ff8000000000000"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    K = int(K)
+    size = max(n, 1) * min(max(K, 1), NEAREST_MAX_K)
+    j, d, cnt = np.zeros(size, dtype=np.int32), np.zeros(size), np.zeros(max(n, 1), dtype=np.int32)
+    _chk(lib, lib.dpr_nearest_host(_p(rows, c_f64p), n, K, _p(j, c_i32p), _p(d, c_f64p), _p(cnt, c_i32p)))
+    return dict(j=j.reshape(n, K), d=d.reshape(n, K), cnt=cnt)
 
 
 FIT_SUMS = ("n", "skipped", "sum_d", "sum_p", "sum_dd", "sum_pp", "sum_dp", "ss", "wss", "n_w", "max_e", "rms", "rms_rel", "explained",
@@ -1231,6 +1254,59 @@ class Dipper:
             self.pairs_end()
         cat = (lambda t, dt: np.concatenate([p[t] for p in parts]) if parts else np.zeros(0, dtype=dt))
         return dict(i=cat(0, np.int32), j=cat(1, np.int32), d=cat(2, np.float64), label=label, stats=stats, info=info)
+
+    def nearest_begin(self, source, dist_type=1, k=15, K=10, block_rows=0):
+        _chk(self.L, self.L.dpr_nearest_begin(self.h, source, dist_type, k, int(K), int(block_rows)))
+
+    def nearest_next(self, K, copy=True):
+        """(j [rows, K], d [rows, K], cnt [rows], row0) of the next row block: copies of the library's pinned arrays (copy=False:
+        views, valid until the next call); rows == 0 behind the last block"""
+        pj, pd, pc = c_i32p(), c_f64p(), c_i32p()
+        row0, rows = C.c_int64(0), C.c_int64(0)
+        _chk(self.L, self.L.dpr_nearest_next(self.h, C.byref(pj), C.byref(pd), C.byref(pc), C.byref(row0), C.byref(rows)))
+        r = rows.value
+        if r == 0:
+            return np.zeros((0, K), dtype=np.int32), np.zeros((0, K)), np.zeros(0, dtype=np.int32), row0.value
+        out = [np.ctypeslib.as_array(pj, (r, K)), np.ctypeslib.as_array(pd, (r, K)), np.ctypeslib.as_array(pc, (r,))]
+        return (*[a.copy() if copy else a for a in out], row0.value)
+
+    def nearest_stats(self):
+        out = np.zeros(6, dtype=np.int64)
+        _chk(self.L, self.L.dpr_nearest_stats(self.h, _p(out, c_i64p)))
+        return {k: int(out[t]) for t, k in enumerate(NEAREST_STATS)}
+
+    def nearest_info(self):
+        """dict(dist_ms, select_ms, copy_ms, block_rows, n) of the stream so far (ms: HIP events, summed over its blocks)"""
+        ms, shape = np.zeros(3), np.zeros(2, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_nearest_info(self.h, _p(ms, c_f64p), _p(shape, c_i64p)))
+        return dict(dist_ms=float(ms[0]), select_ms=float(ms[1]), copy_ms=float(ms[2]), block_rows=int(shape[0]), n=int(shape[1]))
+
+    def nearest_end(self):
+        _chk(self.L, self.L.dpr_nearest_end(self.h))
+
+    def nearest(self, source, dist_type=1, k=15, K=10, block_rows=0, keep=True):
+        """The K nearest neighbours of every sequence of the uploaded source (alignment, sketches, or the matrix of set_matrix_lower),
+        streamed in blocks of block_rows full rows (0: the library's choice) without ever building the matrix: dict(j [n, K], d [n, K],
+        cnt [n], stats, info).  Row i: the columns c != i with a finite distance, nearest first, equal distances by column; behind the
+        cnt[i] real places j is -1 and d NaN.  stats has the keys of NEAREST_STATS, info those of nearest_info.  keep=False: the blocks
+        are dropped (measurement runs)"""
+        self.nearest_begin(source, dist_type, k, K, block_rows)
+        try:
+            n = self.nearest_info()["n"]
+            parts, done = [], 0
+            while done < n:
+                pj, pd, pc, row0 = self.nearest_next(K, copy=keep)
+                assert row0 == done and len(pc) > 0
+                done += len(pc)
+                if keep:
+                    parts.append((pj, pd, pc))
+            stats, info = self.nearest_stats(), self.nearest_info()
+        finally:
+            self.nearest_end()
+        if not keep:
+            return dict(j=None, d=None, cnt=None, stats=stats, info=info)
+        return dict(j=np.concatenate([p[0] for p in parts]), d=np.concatenate([p[1] for p in parts]),
+                    cnt=np.concatenate([p[2] for p in parts]), stats=stats, info=info)
 
     def tree_fit(self, parent, length, n=None):
         """tree_fit_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run); the

@@ -541,6 +541,30 @@ int pairs_write_hook(const double* rows, int64_t ld, bool packed, int64_t r0, in
 int pairs_parent_init(int32_t* parent, int64_t n, hipStream_t s);
 int pairs_flatten(const int32_t* parent, int32_t* out, int64_t n, hipStream_t s);      // out[v] = root of v (out may be parent itself)
 
+// ---- each sequence's K nearest neighbours (nearest.hip; driver in ctx_nearest.hip) ---------------------------------------------------
+// Everything lives from dpr_nearest_begin to dpr_nearest_end (or the next begin, or dpr_destroy), beside and independent of a stream of
+// pairs.  Device memory: one block of full rows (every source: the packed triangle is expanded into it) and block_rows * K results.
+constexpr int kNearestMaxK = 256;                        // 1 <= K <= kNearestMaxK
+constexpr int kNearestThreads = 256;                     // one workgroup walks one row
+constexpr int kNearestChunk = 4 * kNearestThreads;       // columns per step of the walk: two 16-byte loads per lane
+constexpr int kNearestCap = kNearestChunk + 2 * kNearestMaxK;      // candidates held in LDS: a step always fits behind a selection's K
+struct NearestBuffers {
+    int source = 0, dist_type = 0, K = 0;
+    int64_t n = 0, block_rows = 0, ld = 0, next_row = 0;
+    DevBuf<double> block;                // [block_rows][ld] full rows of the current block
+    DevBuf<int32_t> oj, ocnt, oflush;    // [block_rows][K] columns; [block_rows] real entries; [block_rows] selections a row needed before its last
+    DevBuf<double> od;                   // [block_rows][K] distances
+    PinnedBuf hj, hd, hcnt, hflush;      // host side of the four
+    int64_t dev_bytes = 0, peak_bytes = 0;
+    int64_t blocks = 0, neighbours = 0, fewer = 0, none = 0, flushes = 0;
+    double dist_ms = 0, select_ms = 0, copy_ms = 0;      // summed over the blocks (HIP events): the provider (or the expansion); the select; the copies back
+};
+// rows [r0, r0 + nr) of the packed triangle as full rows: out[(i - r0) * ld + j] = D_ij for j < n (0 on the diagonal)
+int nearest_expand_packed(const double* lower, int64_t n, int64_t r0, int64_t nr, double* out, int64_t ld, hipStream_t s);
+// row r0 + t = rows[t * ld + 0 .. n): its K nearest into oj / od [t * K ..], ocnt[t], oflush[t]
+int nearest_select(const double* rows, int64_t ld, int64_t r0, int64_t nr, int64_t n, int K, int32_t* oj, double* od, int32_t* ocnt,
+                   int32_t* oflush, hipStream_t s);
+
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of kIC = 1 024 tips the (value -> tips, positions) postings
 struct MashIndex {

@@ -10,14 +10,16 @@ struct RowSource {
     dpr_ctx* c;
     int source, dist_type;
     // rows [i0, i0 + nr) x columns [0, ncols) into out (row stride ld; transposed: column stride ld); beside: tree kernels of
-    // another stream run during these launches (the only place that sets MashBuffers::share_chip)
-    int fill(int64_t i0, int64_t nr, double* out, int64_t ld, int64_t ncols, hipStream_t st, bool transposed = false, bool beside = false) const
+    // another stream run during these launches (the only place that sets MashBuffers::share_chip); full: a row's columns beyond its own
+    // index are wanted too (the MSA provider writes every column below ncols anyway)
+    int fill(int64_t i0, int64_t nr, double* out, int64_t ld, int64_t ncols, hipStream_t st, bool transposed = false, bool beside = false,
+             bool full = false) const
     {
         if (nr <= 0) return DPR_OK;
         if (source == DPR_SRC_MSA) return msa_dist_block_rows(c->msa, i0, nr, 0, 0, ncols, dist_type, out, ld, st, transposed);
         if (source != DPR_SRC_MASH) return DPR_OK;
         c->mash.share_chip = beside;
-        const int rc = mash_dist_rows(c->mash, i0, nr, 0, 0, false, ncols, out, ld, st, transposed);
+        const int rc = mash_dist_rows(c->mash, i0, nr, 0, 0, full, ncols, out, ld, st, transposed);
         c->mash.share_chip = false;
         return rc;
     }

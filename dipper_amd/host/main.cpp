@@ -309,6 +309,79 @@ int runPairsOutput(const Options& o)
     return 0;
 }
 
+// -o n --nearest K: every sequence's K nearest sequences, from any of the three inputs, uploaded as runPairsOutput uploads them (input
+// order; a distance here is the number -o d prints).  The matrix is never built: the library streams blocks of full rows and returns
+// each row's K best in order (dpr_nearest_begin / _next).
+int runNearestOutput(const Options& o)
+{
+    Param params = o.params;
+    std::vector<std::string> seqs, names_, names;
+    MatrixReader matrixReader;
+    if (params.in == "d") {
+        matrixReader.read(o.inputFile);
+        names = matrixReader.name;
+    } else {
+        readSequences(o.inputFile, seqs, names_);
+        names = names_;      // (input order: shuffledIds(n, -1) is the identity)
+    }
+    const size_t n = names.size();
+    if (n < 2) die("ERROR: need at least two sequences in " + o.inputFile);
+    const std::vector<int> ids = shuffledIds(n, -1);
+    auto output_ = openFile(o.outputFile, "output file");
+    DeviceContext dev(o.device);
+    MSADeviceArrays msaDeviceArrays;
+    MashDeviceArrays mashDeviceArrays;
+    int source = DPR_SRC_MATRIX;
+    if (params.in == "d") {
+        gpuCheck(dpr_set_matrix_lower(dev.ctx, matrixReader.lower.data(), (int64_t)n), "dpr_set_matrix_lower");
+    } else {
+        const bool aligned = params.in == "m";
+        source = aligned ? DPR_SRC_MSA : DPR_SRC_MASH;
+        allocateSequences(dev, aligned, o.protein, PackedSequences(), false, seqs, ids, msaDeviceArrays, mashDeviceArrays);
+        if (!aligned) mashDeviceArrays.sketchConstructionOnGpu(dev, params);
+    }
+    const int K = o.nearestK;
+    gpuCheck(dpr_nearest_begin(dev.ctx, source, (int)params.distanceType, (int)params.kmerSize, K, 0), "dpr_nearest_begin");
+    *output_ << "ID\tRank\tNeighbour\tDistance\n";
+    std::string text;
+    char buf[64];
+    int64_t done = 0;
+    while (done < (int64_t)n) {
+        const int32_t *pj = nullptr, *pc = nullptr;
+        const double* pd = nullptr;
+        int64_t row0 = 0, rows = 0;
+        gpuCheck(dpr_nearest_next(dev.ctx, &pj, &pd, &pc, &row0, &rows), "dpr_nearest_next");
+        if (rows <= 0 || row0 != done) die("ERROR: dpr_nearest_next: the stream ended before the last sequence");
+        text.clear();
+        for (int64_t t = 0; t < rows; ++t)
+            for (int32_t r = 0; r < pc[t]; ++r) {
+                text += names[(size_t)(row0 + t)];
+                std::snprintf(buf, sizeof(buf), "\t%d\t", (int)r + 1);
+                text += buf;
+                text += names[(size_t)pj[t * K + r]];
+                std::snprintf(buf, sizeof(buf), "\t%.9g\n", pd[t * K + r]);
+                text += buf;
+            }
+        output_->write(text.data(), (std::streamsize)text.size());
+        done = row0 + rows;
+    }
+    int64_t stats[6] = { 0, 0, 0, 0, 0, 0 };
+    gpuCheck(dpr_nearest_stats(dev.ctx, stats), "dpr_nearest_stats");
+    if (cliLog()) {
+        double ms[3] = { 0, 0, 0 };
+        int64_t shape[2] = { 0, 0 };
+        dpr_get_nearest_info(dev.ctx, ms, shape);
+        std::cerr << "  device: " << stats[0] << " blocks of " << shape[0] << " rows; distances " << ms[0] << " ms, select " << ms[1] << " ms ("
+                  << stats[4] << " early selections), copies " << ms[2] << " ms; peak device bytes " << stats[5] << "\n";
+    }
+    gpuCheck(dpr_nearest_end(dev.ctx), "dpr_nearest_end");
+    output_->flush();
+    if (!*output_) die("ERROR: cannot write output file: " + o.outputFile);
+    std::cerr << "Nearest: " << stats[1] << " neighbours of " << n << " sequences (" << K << " asked; " << stats[2] << " sequences with fewer, " << stats[3]
+              << " with none)\n";
+    return 0;
+}
+
 // -i m / -i r -o t: the tree of the sequences, in the mode their number selects.  This is the timed path: the order of its steps is kept
 int runFromSequences(const Options& o, Clock::time_point inputStart)
 {
@@ -491,6 +564,7 @@ int main(int argc, char** argv)
     if (o.add) return runAdd(o, inputStart);
     if (sequences && o.params.out == "d") return runDistanceOutput(o);
     if (o.pairs && (sequences || o.params.in == "d")) return runPairsOutput(o);
+    if (o.nearest && (sequences || o.params.in == "d")) return runNearestOutput(o);
     if (sequences && o.params.out == "t") return runFromSequences(o, inputStart);
     if (o.params.in == "d" && o.params.out == "t") return runFromMatrix(o);
     std::printf("Invalid input-output combinations!!!!!\n");

@@ -29,6 +29,8 @@ const char* const kHelp =
     "                                    -i m or -i r; with --bootstrap: placement support per edge)\n"
     "                                p - the pairs of sequences within a distance threshold (needs --within;\n"
     "                                    -i m, r or d), as a table; no tree and no matrix is built\n"
+    "                                n - the nearest neighbours of every sequence (needs --nearest; -i m, r or\n"
+    "                                    d), as a table; no tree and no matrix is built\n"
     "  -m [ --algorithm ] arg      Algorithm selection:\n"
     "                                0 - default mode\n"
     "                                1 - force placement\n"
@@ -141,6 +143,17 @@ const char* const kHelp =
     "                              of the pairs -- to file arg: a `#` line with the totals, then every sequence\n"
     "                              in input order with the number of its cluster (clusters numbered from 1 by\n"
     "                              their first sequence).  Computed on the GPU\n"
+    "  --nearest arg               With -o n: the number K of neighbours, a whole number from 1 to 256.  The output\n"
+    "                              file gets the line `ID<TAB>Rank<TAB>Neighbour<TAB>Distance`, then for every\n"
+    "                              sequence in input order its K nearest sequences, nearest first (rank 1, 2,\n"
+    "                              ...; equal distances in input order), with the distance -o d prints for the\n"
+    "                              pair.  A distance that is not a number or infinite makes no neighbour: a\n"
+    "                              sequence may have fewer than K lines, or none.  Input order is kept (--seed,\n"
+    "                              -m and -p are not consulted).  The distances are computed on the GPU a block\n"
+    "                              of rows at a time and the K best of every row are selected there: the matrix\n"
+    "                              is never held.  One line `Nearest:` on stderr.  Valid where -o p is: -i m with\n"
+    "                              every -d, --protein, --site-coverage / --complete-deletion; -i r with -k /\n"
+    "                              -s; -i d; one GPU.  Not with --add, -t, a tree option, --within or --clusters\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -171,7 +184,7 @@ static const Opt kOpts[] = {
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
     { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
     { "site-coverage", 0, true }, { "complete-deletion", 0, false }, { "fit", 0, false }, { "fit-taxa", 0, true }, { "dump-newick", 0, true },
-    { "within", 0, true }, { "clusters", 0, true },
+    { "within", 0, true }, { "clusters", 0, true }, { "nearest", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -355,7 +368,7 @@ Options parseOptions(int argc, char** argv)
     auto treeBuilder = [&](const std::string& label, const char* wording, const char* noBootstrap, bool one_gpu) {
         if (o.algo == "1" || o.algo == "3") usageError(label + wording + " (-m 2, or the default mode below 30000 sequences)");
         if (o.add) usageError(label + " is not supported with --add");
-        if (params.out == "d" || params.out == "j" || params.out == "p") usageError(label + " needs tree output (-o t)");
+        if (params.out == "d" || params.out == "j" || params.out == "p" || params.out == "n") usageError(label + " needs tree output (-o t)");
         if (noBootstrap && has("bootstrap")) usageError(label + " is not supported with --bootstrap (" + noBootstrap + ")");
         if (o.njOnly.empty()) o.njOnly = label + wording;
         if (one_gpu) oneGpu.push_back(label);
@@ -442,6 +455,20 @@ Options parseOptions(int argc, char** argv)
             if (o.clustersFile == o.outputFile) usageError("--clusters: the file must differ from the output file (-O)");
         }
         oneGpu.push_back("-o p");
+    }
+    // -o n: the nearest neighbours of every sequence
+    o.nearest = params.out == "n";
+    if (has("nearest") && !o.nearest) usageError("--nearest needs the neighbour output (-o n)");
+    if (o.nearest) {
+        if (!has("nearest")) usageError("-o n needs the number of neighbours (--nearest K)");
+        const std::string& kv = vm.at("nearest");
+        bool digits = !kv.empty() && kv.size() <= 9;
+        for (char ch : kv) digits = digits && std::isdigit((unsigned char)ch);
+        o.nearestK = digits ? std::stoi(kv) : 0;
+        if (o.nearestK < 1 || o.nearestK > DPR_NEAREST_MAX_K) usageError("--nearest: the number of neighbours must be a whole number from 1 to 256");
+        if (o.add || has("input-tree")) usageError("-o n is not supported with --add or -t (it compares the sequences of one input with each other)");
+        if (has("bootstrap")) usageError("--bootstrap needs tree output (-o t)");
+        oneGpu.push_back("-o n");
     }
     parseBootstrap(vm, o);
 

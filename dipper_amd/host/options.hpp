@@ -23,6 +23,8 @@ struct Options {
     bool pairs = false;          // -o p: the pairs within --within and, with --clusters, the clusters they form
     double within = 0;           // --within T, a finite number >= 0 ...
     std::string withinText;      // ... and T as it was given (the reports name it so)
+    bool nearest = false;        // -o n: the --nearest K nearest neighbours of every sequence
+    int nearestK = 0;
     std::string siteText;
     long long seed = 1;
     int device = 0;

@@ -858,6 +858,45 @@ int dpr_pairs_within_host(const double *lower_rows, int64_t n, double threshold,
  * rank of every tip's component, components ordered by their smallest member.  Labels that are not component minima: DPR_ERR_ARG. */
 int dpr_pairs_summary_host(const int32_t *label, int64_t n, int64_t out3[3], int32_t *rank);
 
+/* ---- Each sequence's K nearest neighbours (the command's -o n; no reference counterpart) --------------------------------------------
+ * Contract.  Over the n tips of a source, with D_ij the entry dpr_dist_matrix would give the pair (read as a symmetric matrix): the
+ *   candidates of row i are the columns j != i whose D_ij is finite -- a NaN, +inf and -inf are never neighbours.  Candidate a comes
+ *   before candidate b when d_a < d_b in fp64, or d_a == d_b and j_a < j_b (-0.0 == +0.0: the two tie and the column decides).  Row i's
+ *   result is the first min(K, candidates) of that order, in that order; d is D_ij bit for bit (a -0.0 stays -0.0).  The places behind
+ *   them, up to K, hold j = -1 and d = the NaN 0x7ff8000000000000; cnt[i] says how many places are real.  1 <= K <= DPR_NEAREST_MAX_K,
+ *   n >= 2, one rank.  The answer is a function of the matrix alone: nothing depends on block_rows, on a launch geometry or on the
+ *   order in which wavefronts finish.
+ * dpr_nearest_begin starts a stream over the uploaded alignment (DPR_SRC_MSA, dist_type as dpr_dist_matrix takes it), the sketches
+ *   (DPR_SRC_MASH, k the sketch k) or the triangle of dpr_set_matrix_lower (DPR_SRC_MATRIX); DPR_ERR_STATE without that input.  K
+ *   outside 1 .. 256, a negative block_rows, fewer than two tips, several ranks, virtual ranks: DPR_ERR_ARG.  A stream of neighbours
+ *   still open on the context is dropped; a stream of pairs (dpr_pairs_*) on the same context is a separate thing and is left alone.
+ *   block_rows: as dpr_pairs_begin takes it (at most 32 768 and n; 0 = the rows that put the block at 1 GiB or less, in whole multiples
+ *   of 64).
+ * Memory.  The n x n matrix is never allocated.  The device holds one block of FULL rows, 8 x block_rows x n bytes (n rounded up to 16
+ *   columns; for DPR_SRC_MATRIX too: the block is expanded from the triangle so that one kernel serves every source), and per row of
+ *   the block 12 K bytes of results and 8 bytes of counts: O(block_rows n) + O(block_rows K).
+ * State.  The context's inputs, its matrix and its NJ state are not touched.
+ * dpr_nearest_next computes the next block: rows [*row0, *row0 + *rows) x all n columns by the source's row provider (symmetry is not
+ *   exploited), then per row one pass that keeps the K best.  *j and *d point at *rows x K entries (row t of the block at t K), *cnt at
+ *   *rows counts, in pinned host memory the library owns, valid until the next call on the context's stream of neighbours.  After the
+ *   last block: *rows == 0, *row0 == n, the pointers NULL, and every later call says the same.  DPR_ERR_STATE before dpr_nearest_begin.
+ * dpr_nearest_stats: out[0] blocks computed, 1 neighbours delivered (the sum of the counts), 2 rows with fewer than K, 3 rows with
+ *   none, 4 the times a row's candidate buffer was cut back to its K best before the end of the row (summed over the rows: a measure
+ *   of the work, not part of the answer), 5 the largest number of bytes of device memory the stream held at any time.
+ * dpr_nearest_end releases everything the stream holds (also done by dpr_destroy); without a stream it does nothing. */
+#define DPR_NEAREST_MAX_K 256
+int dpr_nearest_begin(dpr_ctx *ctx, int source, int dist_type, int k, int K, int64_t block_rows);
+int dpr_nearest_next(dpr_ctx *ctx, const int32_t **j, const double **d, const int32_t **cnt, int64_t *row0, int64_t *rows);
+int dpr_nearest_stats(dpr_ctx *ctx, int64_t out[6]);
+int dpr_nearest_end(dpr_ctx *ctx);
+/* of the stream so far (either may be NULL).  ms: summed over its blocks (HIP events) the row provider (DPR_SRC_MATRIX: the expansion of
+ * the triangle); the select; the copies of the results to the host.  shape: the rows of a block as dpr_nearest_begin settled them, n. */
+int dpr_get_nearest_info(dpr_ctx *ctx, double ms[3], int64_t shape[2]);
+/* host only, no GPU: the contract restated as a loop over the rows with a partial sort under the order above -- on purpose not the
+ * device's algorithm -- the reference of the GPU tests.  lower_rows: the strict lower triangle row by row, as dpr_set_matrix_lower
+ * takes it; j, d: n x K entries; cnt: n.  n < 2, K outside 1 .. 256, a null pointer: DPR_ERR_ARG, nothing written. */
+int dpr_nearest_host(const double *lower_rows, int64_t n, int K, int32_t *j, double *d, int32_t *cnt);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
