@@ -206,6 +206,11 @@ def load_library():
     L.dpr_nearest_end.argtypes = [C.c_void_p]
     L.dpr_get_nearest_info.argtypes = [C.c_void_p, c_f64p, c_i64p]
     L.dpr_nearest_host.argtypes = [c_f64p, C.c_int64, C.c_int, c_i32p, c_f64p, c_i32p]
+    L.dpr_mst_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, c_i32p, c_i32p, c_f64p, c_i64p, c_i32p]
+    L.dpr_mst_stats.argtypes = [C.c_void_p, c_i64p]
+    L.dpr_get_mst_info.argtypes = [C.c_void_p, c_f64p, c_i64p]
+    L.dpr_mst_host.argtypes = [c_f64p, C.c_int64, c_i32p, c_i32p, c_f64p, c_i64p, c_i32p]
+    L.dpr_mst_dendrogram_host.argtypes = [C.c_int64, c_i32p, c_i32p, c_f64p, C.c_int64, c_i32p, c_i32p, c_f64p]
     _LIB = L
     return L
 
@@ -553,6 +558,36 @@ def nearest_host(D, K):
     return dict(j=j.reshape(n, K), d=d.reshape(n, K), cnt=cnt)
 
 
+MST_STATS = ("rounds", "blocks", "edges", "components", "largest", "singletons", "peak_device_bytes", "rows_walked")
+
+
+def mst_host(D):
+    """The minimum spanning forest of the (n, n) array D, whose strict lower triangle is read as a symmetric matrix, by Kruskal on the
+    host (no GPU): dict(i, j, d, label) as Dipper.mst returns them.  The E = n - components edges ascending by (key of the distance,
+    i, j), i > j, d the entry's own bits; a NaN or infinite entry makes no edge; label[v] the smallest index of v's component"""
+    lib = load_library()
+    n, rows = _lower_rows(D)
+    cap = max(n - 1, 1)
+    i, j, d, label = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(max(n, 1), dtype=np.int32)
+    E = C.c_int64(0)
+    _chk(lib, lib.dpr_mst_host(_p(rows, c_f64p), n, _p(i, c_i32p), _p(j, c_i32p), _p(d, c_f64p), C.byref(E), _p(label, c_i32p)))
+    return dict(i=i[: E.value], j=j[: E.value], d=d[: E.value], label=label)
+
+
+def mst_dendrogram_host(n, i, j, d):
+    """The single-linkage dendrogram of a connected forest over n tips (the n - 1 edges of mst_host / Dipper.mst, in their order) as a
+    merge log in the slot convention of upgma: dict(merge_x, merge_y, height), n - 1 entries each, height 0.5 * d.  tree_from_upgma
+    takes it as it is.  Edges that do not connect the tips are refused"""
+    lib = load_library()
+    i, j = (np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1)) for a in (i, j))
+    d = np.ascontiguousarray(np.asarray(d, dtype=np.float64).reshape(-1))
+    assert len(i) == len(j) == len(d)
+    cnt = max(int(n) - 1, 1)
+    mx, my, h = np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32), np.zeros(cnt)
+    _chk(lib, lib.dpr_mst_dendrogram_host(int(n), _p(i, c_i32p), _p(j, c_i32p), _p(d, c_f64p), len(i), _p(mx, c_i32p), _p(my, c_i32p), _p(h, c_f64p)))
+    return dict(merge_x=mx[: n - 1], merge_y=my[: n - 1], height=h[: n - 1])
+
+
 FIT_SUMS = ("n", "skipped", "sum_d", "sum_p", "sum_dd", "sum_pp", "sum_dp", "ss", "wss", "n_w", "max_e", "rms", "rms_rel", "explained",
             "cophenetic", "spare")
 
@@ -782,6 +817,7 @@ class Dipper:
         p = np.ascontiguousarray(packed4, dtype=np.uint64)
         _chk(self.L, self.L.dpr_set_msa(self.h, _p(p, c_u64p), p.shape[0], L))
         self._msa_sites = int(L)      # (msa_site_coverage sizes its result by it)
+        self._tips = {**getattr(self, "_tips", {}), SRC_MSA: int(p.shape[0])}      # (mst sizes its results by the source's tips)
 
     def set_msa_aa(self, codes):
         """protein alignment: codes [n][L] uint8 as pack_aa_many builds them (>= 20: not a residue); source stays SRC_MSA"""
@@ -789,11 +825,13 @@ class Dipper:
         assert p.ndim == 2
         _chk(self.L, self.L.dpr_set_msa_aa(self.h, _p(p, C.POINTER(C.c_uint8)), p.shape[0], p.shape[1]))
         self._msa_sites = int(p.shape[1])
+        self._tips = {**getattr(self, "_tips", {}), SRC_MSA: int(p.shape[0])}
 
     def set_matrix_lower(self, rows, n):
         r = np.ascontiguousarray(rows, dtype=np.float64)
         assert r.size == n * (n - 1) // 2
         _chk(self.L, self.L.dpr_set_matrix_lower(self.h, _p(r, c_f64p), n))
+        self._tips = {**getattr(self, "_tips", {}), SRC_MATRIX: int(n)}
 
     def set_matrix_full(self, D):
         """Convenience: takes an (n,n) array and hands over its strict lower triangle row by row."""
@@ -814,6 +852,7 @@ class Dipper:
             flat = np.zeros(1, np.uint64)
         self._reads = (np.ascontiguousarray(flat), off, lens)
         _chk(self.L, self.L.dpr_set_reads(self.h, _p(self._reads[0], c_u64p), _p(off, c_u64p), _p(lens, c_u64p), len(seqs)))
+        self._tips = {**getattr(self, "_tips", {}), SRC_MASH: len(seqs)}
 
     def set_reads_packed(self, flat, off, lens):
         """already 2-bit packed reads: the three arrays of dpr_set_reads (twoBitCompressor layout)"""
@@ -822,6 +861,7 @@ class Dipper:
         lens = np.ascontiguousarray(lens, dtype=np.uint64)
         self._reads = (flat, off, lens)
         _chk(self.L, self.L.dpr_set_reads(self.h, _p(flat, c_u64p), _p(off, c_u64p), _p(lens, c_u64p), len(lens)))
+        self._tips = {**getattr(self, "_tips", {}), SRC_MASH: len(lens)}
 
     def sketch(self, k=15, S=1000, fetch=True):
         n = len(self._reads[2])
@@ -1307,6 +1347,30 @@ class Dipper:
             return dict(j=None, d=None, cnt=None, stats=stats, info=info)
         return dict(j=np.concatenate([p[0] for p in parts]), d=np.concatenate([p[1] for p in parts]),
                     cnt=np.concatenate([p[2] for p in parts]), stats=stats, info=info)
+
+    def mst_stats(self):
+        out = np.zeros(8, dtype=np.int64)
+        _chk(self.L, self.L.dpr_mst_stats(self.h, _p(out, c_i64p)))
+        return {k: int(out[t]) for t, k in enumerate(MST_STATS)}
+
+    def mst_info(self):
+        """dict(dist_ms, rowmin_ms, round_ms, block_rows, n) of the last mst (ms: HIP events, summed over its rounds)"""
+        ms, shape = np.zeros(3), np.zeros(2, dtype=np.int64)
+        _chk(self.L, self.L.dpr_get_mst_info(self.h, _p(ms, c_f64p), _p(shape, c_i64p)))
+        return dict(dist_ms=float(ms[0]), rowmin_ms=float(ms[1]), round_ms=float(ms[2]), block_rows=int(shape[0]), n=int(shape[1]))
+
+    def mst(self, source, dist_type=1, k=15, block_rows=0):
+        """The minimum spanning forest of the distances of the uploaded source (alignment, sketches, or the matrix of set_matrix_lower),
+        by Boruvka rounds over streamed blocks of block_rows full rows (0: the library's choice) without ever building the matrix:
+        dict(i, j, d, label, stats, info).  The edges ascending by (key of the distance, i, j), i > j; label[v] the smallest index of
+        v's component; stats has the keys of MST_STATS, info those of mst_info"""
+        n = getattr(self, "_tips", {}).get(source, 0)      # (nothing uploaded: the library says so)
+        cap = max(n - 1, 1)
+        i, j, d, label = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap), np.zeros(max(n, 1), dtype=np.int32)
+        E = C.c_int64(0)
+        _chk(self.L, self.L.dpr_mst_run(self.h, source, dist_type, k, int(block_rows), _p(i, c_i32p), _p(j, c_i32p), _p(d, c_f64p), C.byref(E),
+                                        _p(label, c_i32p)))
+        return dict(i=i[: E.value], j=j[: E.value], d=d[: E.value], label=label, stats=self.mst_stats(), info=self.mst_info())
 
     def tree_fit(self, parent, length, n=None):
         """tree_fit_host's result, computed on the device from the context's fresh matrix (after dist_matrix, before nj_run); the

@@ -184,6 +184,7 @@ int dpr_destroy(dpr_ctx* c)
     tbe_free(c->tbe);
     c->pairs.reset();
     c->nearest.reset();
+    c->mst.reset();
     if (c->place_trace) (void)hipFree(c->place_trace);
     if (c->packed_lower) (void)hipFree(c->packed_lower);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);

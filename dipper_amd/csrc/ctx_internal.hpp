@@ -67,6 +67,7 @@ struct dpr_ctx {
     dpr::FitBuffers fit;             // dpr_tree_fit: the tree's lookup tables and the per-taxon parts
     std::unique_ptr<dpr::PairsBuffers> pairs;    // dpr_pairs_begin .. dpr_pairs_end: the stream in progress, else empty
     std::unique_ptr<dpr::NearestBuffers> nearest;      // dpr_nearest_begin .. dpr_nearest_end: likewise, independent of pairs
+    std::unique_ptr<dpr::MstState> mst;          // the figures of the last dpr_mst_run (its buffers live for the call only)
     int tbe_lds = 0;                 // test hook (dpr_ctx_set_tbe_lds): LDS bytes for the transfer kernel's tables, 0 = its own rule
     double* place_trace = nullptr;   // [3N] (eid, frac, add) per placed tip
     double* packed_lower = nullptr;  // MATRIX source, device

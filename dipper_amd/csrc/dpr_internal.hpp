@@ -540,6 +540,7 @@ int pairs_write_hook(const double* rows, int64_t ld, bool packed, int64_t r0, in
                      int32_t* pi, int32_t* pj, double* pd, int32_t* parent, int64_t n, hipStream_t s);
 int pairs_parent_init(int32_t* parent, int64_t n, hipStream_t s);
 int pairs_flatten(const int32_t* parent, int32_t* out, int64_t n, hipStream_t s);      // out[v] = root of v (out may be parent itself)
+int pairs_hook(const int32_t* pi, const int32_t* pj, int64_t total, int32_t* parent, int64_t n, hipStream_t s);      // the union of `total` pairs into the forest (device arrays)
 
 // ---- each sequence's K nearest neighbours (nearest.hip; driver in ctx_nearest.hip) ---------------------------------------------------
 // Everything lives from dpr_nearest_begin to dpr_nearest_end (or the next begin, or dpr_destroy), beside and independent of a stream of
@@ -559,11 +560,43 @@ struct NearestBuffers {
     int64_t blocks = 0, neighbours = 0, fewer = 0, none = 0, flushes = 0;
     double dist_ms = 0, select_ms = 0, copy_ms = 0;      // summed over the blocks (HIP events): the provider (or the expansion); the select; the copies back
 };
+// the sortable key of a distance: the bits of d (of +0.0 for either zero) with the sign bit flipped for d >= 0 and all bits flipped for
+// d < 0 -- unsigned order of the keys = fp64 order of the finite distances (nearest.hip, mst.hip)
+__device__ inline unsigned long long nearest_key(double d)
+{
+    unsigned long long b = d == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(d);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ inline bool nearest_finite(double d)
+{
+    return ((unsigned long long)__double_as_longlong(d) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
 // rows [r0, r0 + nr) of the packed triangle as full rows: out[(i - r0) * ld + j] = D_ij for j < n (0 on the diagonal)
 int nearest_expand_packed(const double* lower, int64_t n, int64_t r0, int64_t nr, double* out, int64_t ld, hipStream_t s);
 // row r0 + t = rows[t * ld + 0 .. n): its K nearest into oj / od [t * K ..], ocnt[t], oflush[t]
 int nearest_select(const double* rows, int64_t ld, int64_t r0, int64_t nr, int64_t n, int K, int32_t* oj, double* od, int32_t* ocnt,
                    int32_t* oflush, hipStream_t s);
+
+// ---- the minimum spanning forest of the distances (mst.hip; driver in ctx_mst.hip) -------------------------------------------------------
+// Boruvka rounds over streamed blocks of full rows.  What a call allocates lives for the call; the context keeps the figures of the last
+// one (dpr_mst_stats, dpr_get_mst_info).
+constexpr int kMstThreads = 256;                         // one workgroup walks one row
+constexpr int kMstChunk = 4 * kMstThreads;               // columns per step of the walk: two 16-byte loads per lane
+struct MstState {
+    int64_t n = 0, block_rows = 0;
+    int64_t rounds = 0, blocks = 0, edges = 0, comps = 0, largest = 0, singletons = 0, peak_bytes = 0, rows_walked = 0;
+    double dist_ms = 0, rowmin_ms = 0, round_ms = 0;      // summed over the rounds (HIP events): the provider (or the expansion); the row minimum; the component work and the copies
+};
+// row r0 + t = rows[t * ld + 0 .. n): the smallest (key, c) over the columns c < n with label[c] != label[r0 + t] and a finite entry
+// into rkey / rcol / rdist [r0 + t] (rdist: that entry's own bits); an all-ones key, column -1 for none.  label: ld entries readable.
+int mst_row_min(const double* rows, int64_t ld, int64_t r0, int64_t nr, int64_t n, const int32_t* label, unsigned long long* rkey,
+                int32_t* rcol, double* rdist, hipStream_t s);
+// per component (named by its root, label[v] == v) the smallest (key, max(r, c), min(r, c)) of its rows into ckey / cedge, both all-ones
+// before; then every root with an edge appends it behind *count in ei / ej / ed (cap places) unless the component at the other end
+// chose the same edge and has the smaller label
+int mst_component_min_emit(const int32_t* label, const unsigned long long* rkey, const int32_t* rcol, const double* rdist, int64_t n,
+                           unsigned long long* ckey, unsigned long long* cedge, int32_t* ei, int32_t* ej, double* ed, int64_t cap,
+                           unsigned long long* count, hipStream_t s);
 
 // mash.hip
 // inverted index over the sketches (mash_index.hip): per chunk of kIC = 1 024 tips the (value -> tips, positions) postings

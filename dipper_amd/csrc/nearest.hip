@@ -35,17 +35,6 @@ constexpr int kNearestCutMin = 128;                    // the fewest held candid
 constexpr int kExpandTile = 64;
 static_assert(kNearestCap % kNearestThreads == 0 && kNearestCap - kNearestChunk >= kNearestMaxK, "a selection's K and a step fit");
 
-__device__ inline unsigned long long nearest_key(double d)
-{
-    unsigned long long b = d == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-
-__device__ inline bool nearest_finite(double d)
-{
-    return ((unsigned long long)__double_as_longlong(d) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
 __device__ inline bool nearest_before(unsigned long long ka, int32_t ja, unsigned long long kb, int32_t jb)
 {
     return ka < kb || (ka == kb && ja < jb);

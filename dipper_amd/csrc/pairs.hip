@@ -195,6 +195,14 @@ int pairs_write_hook(const double* rows, int64_t ld, bool packed, int64_t r0, in
     return pairs_flatten(parent, parent, n, s);
 }
 
+int pairs_hook(const int32_t* pi, const int32_t* pj, int64_t total, int32_t* parent, int64_t n, hipStream_t s)
+{
+    if (total <= 0) return DPR_OK;
+    hipLaunchKernelGGL(pairs_hook_kernel, dim3(pairs_grid(total)), dim3(kPairsThreads), 0, s, pi, pj, total, parent, n);
+    DPR_HIP(hipGetLastError());
+    return DPR_OK;
+}
+
 int pairs_parent_init(int32_t* parent, int64_t n, hipStream_t s)
 {
     hipLaunchKernelGGL(pairs_iota_kernel, dim3(pairs_grid(n)), dim3(kPairsThreads), 0, s, parent, n);

@@ -382,6 +382,91 @@ int runNearestOutput(const Options& o)
     return 0;
 }
 
+// -o s [--dendrogram FILE]: the minimum spanning tree of the distances (of every component, where non-finite distances separate some),
+// from any of the three inputs, uploaded as runPairsOutput uploads them (input order: ties resolve in input order; a distance here is
+// the number -o d prints).  The matrix is never built: the library runs Boruvka's rounds over streamed blocks of full rows and returns
+// the edges in the contract's order (dpr_mst_run).  The dendrogram is the edges again, as a UPGMA-style merge log.
+int runMstOutput(const Options& o)
+{
+    Param params = o.params;
+    std::vector<std::string> seqs, names_, names;
+    MatrixReader matrixReader;
+    if (params.in == "d") {
+        matrixReader.read(o.inputFile);
+        names = matrixReader.name;
+    } else {
+        readSequences(o.inputFile, seqs, names_);
+        names = names_;      // (input order: shuffledIds(n, -1) is the identity)
+    }
+    const size_t n = names.size();
+    if (n < 2) die("ERROR: need at least two sequences in " + o.inputFile);
+    const std::vector<int> ids = shuffledIds(n, -1);
+    auto output_ = openFile(o.outputFile, "output file");
+    DeviceContext dev(o.device);
+    MSADeviceArrays msaDeviceArrays;
+    MashDeviceArrays mashDeviceArrays;
+    int source = DPR_SRC_MATRIX;
+    if (params.in == "d") {
+        gpuCheck(dpr_set_matrix_lower(dev.ctx, matrixReader.lower.data(), (int64_t)n), "dpr_set_matrix_lower");
+    } else {
+        const bool aligned = params.in == "m";
+        source = aligned ? DPR_SRC_MSA : DPR_SRC_MASH;
+        allocateSequences(dev, aligned, o.protein, PackedSequences(), false, seqs, ids, msaDeviceArrays, mashDeviceArrays);
+        if (!aligned) mashDeviceArrays.sketchConstructionOnGpu(dev, params);
+    }
+    std::vector<int32_t> ei(n - 1), ej(n - 1), label(n);
+    std::vector<double> ed(n - 1);
+    int64_t edges = 0;
+    gpuCheck(dpr_mst_run(dev.ctx, source, (int)params.distanceType, (int)params.kmerSize, 0, ei.data(), ej.data(), ed.data(), &edges, label.data()),
+             "dpr_mst_run");
+    int64_t stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    gpuCheck(dpr_mst_stats(dev.ctx, stats), "dpr_mst_stats");
+    if (cliLog()) {
+        double ms[3] = { 0, 0, 0 };
+        int64_t shape[2] = { 0, 0 };
+        dpr_get_mst_info(dev.ctx, ms, shape);
+        std::cerr << "  device: " << stats[0] << " rounds, " << stats[1] << " blocks of " << shape[0] << " rows; distances " << ms[0] << " ms, row minimum "
+                  << ms[1] << " ms, components and copies " << ms[2] << " ms; peak device bytes " << stats[6] << "\n";
+    }
+    *output_ << "ID1\tID2\tDistance\n";
+    std::string text;
+    char buf[64];
+    double length = 0.0;      // summed in file order
+    for (int64_t t = 0; t < edges; ++t) {
+        text += names[(size_t)ei[(size_t)t]];
+        text += '\t';
+        text += names[(size_t)ej[(size_t)t]];
+        std::snprintf(buf, sizeof(buf), "\t%.9g\n", ed[(size_t)t]);
+        text += buf;
+        length += ed[(size_t)t];
+        if (text.size() >= (1u << 20) || t + 1 == edges) { output_->write(text.data(), (std::streamsize)text.size()); text.clear(); }
+    }
+    output_->flush();
+    if (!*output_) die("ERROR: cannot write output file: " + o.outputFile);
+    std::snprintf(buf, sizeof(buf), "%.9g", length);
+    std::cerr << "MST: " << edges << " edges over " << n << " sequences (" << stats[3] << " components, largest " << stats[4] << ", " << stats[5]
+              << " singletons), " << stats[0] << " rounds, length " << buf;
+    if (edges > 0) {
+        std::snprintf(buf, sizeof(buf), "%.9g", ed[(size_t)(edges - 1)]);
+        std::cerr << ", longest edge " << names[(size_t)ei[(size_t)(edges - 1)]] << " / " << names[(size_t)ej[(size_t)(edges - 1)]] << " (" << buf << ")";
+    }
+    std::cerr << "\n";
+    if (o.dendrogramFile.empty()) return 0;
+    if (stats[3] > 1) {
+        std::cerr << "ERROR: no dendrogram: the distances leave " << stats[3] << " components (a distance that is not a number or infinite joins nothing); "
+                  << o.dendrogramFile << " is not written\n";
+        return 1;
+    }
+    std::vector<int32_t> mx(n - 1), my(n - 1);
+    std::vector<double> height(n - 1);
+    gpuCheck(dpr_mst_dendrogram_host((int64_t)n, ei.data(), ej.data(), ed.data(), edges, mx.data(), my.data(), height.data()), "dpr_mst_dendrogram_host");
+    auto tree_ = openFile(o.dendrogramFile, "the --dendrogram file");
+    writeNewickFromUpgma(*tree_, names, mx, my, height);
+    tree_->flush();
+    if (!*tree_) die("ERROR: cannot write the --dendrogram file: " + o.dendrogramFile);
+    return 0;
+}
+
 // -i m / -i r -o t: the tree of the sequences, in the mode their number selects.  This is the timed path: the order of its steps is kept
 int runFromSequences(const Options& o, Clock::time_point inputStart)
 {
@@ -565,6 +650,7 @@ int main(int argc, char** argv)
     if (sequences && o.params.out == "d") return runDistanceOutput(o);
     if (o.pairs && (sequences || o.params.in == "d")) return runPairsOutput(o);
     if (o.nearest && (sequences || o.params.in == "d")) return runNearestOutput(o);
+    if (o.mst && (sequences || o.params.in == "d")) return runMstOutput(o);
     if (sequences && o.params.out == "t") return runFromSequences(o, inputStart);
     if (o.params.in == "d" && o.params.out == "t") return runFromMatrix(o);
     std::printf("Invalid input-output combinations!!!!!\n");

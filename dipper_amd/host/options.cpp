@@ -31,6 +31,8 @@ const char* const kHelp =
     "                                    -i m, r or d), as a table; no tree and no matrix is built\n"
     "                                n - the nearest neighbours of every sequence (needs --nearest; -i m, r or\n"
     "                                    d), as a table; no tree and no matrix is built\n"
+    "                                s - the minimum spanning tree of the distances (-i m, r or d), as a table of\n"
+    "                                    its edges; no matrix is built\n"
     "  -m [ --algorithm ] arg      Algorithm selection:\n"
     "                                0 - default mode\n"
     "                                1 - force placement\n"
@@ -154,6 +156,22 @@ const char* const kHelp =
     "                              is never held.  One line `Nearest:` on stderr.  Valid where -o p is: -i m with\n"
     "                              every -d, --protein, --site-coverage / --complete-deletion; -i r with -k /\n"
     "                              -s; -i d; one GPU.  Not with --add, -t, a tree option, --within or --clusters\n"
+    "  --dendrogram arg            With -o s: write the single-linkage dendrogram to file arg, a rooted ultrametric\n"
+    "                              tree in Newick format (an edge of the spanning tree joins its two sides at\n"
+    "                              half its distance).  When the distances leave several components there is\n"
+    "                              no such tree: the edge file is written, the reason goes to stderr and the\n"
+    "                              exit status is 1.  -o s itself: the output file gets the line\n"
+    "                              `ID1<TAB>ID2<TAB>Distance`, then one line per edge of the minimum spanning\n"
+    "                              tree (of every component, when a distance that is not a number or infinite\n"
+    "                              separates some), shortest first, equal distances by the later sequence of\n"
+    "                              the pair in input order and then the earlier one, with the distance -o d\n"
+    "                              prints for the pair.  Cutting the list at a distance T gives the clusters\n"
+    "                              of -o p --within T.  Input order is kept (--seed, -m and -p are not\n"
+    "                              consulted).  The distances are computed on the GPU a block of rows at a\n"
+    "                              time, once per round of Boruvka's algorithm: the matrix is never held.  One\n"
+    "                              line `MST:` on stderr.  Valid where -o n is: -i m with every -d, --protein,\n"
+    "                              --site-coverage / --complete-deletion; -i r with -k / -s; -i d; one GPU.\n"
+    "                              Not with --add, -t, a tree option, --within, --clusters or --nearest\n"
     "  --bootstrap arg             Felsenstein bootstrap: arg >= 1 replicate alignments (columns drawn\n"
     "                              with replacement); the NJ tree's internal nodes are labelled with\n"
     "                              the percentage of replicate trees that hold their split.\n"
@@ -184,7 +202,7 @@ static const Opt kOpts[] = {
     { "bootstrap-taxa", 0, true }, { "bootstrap-taxa-cutoff", 0, true }, { "protein", 0, false },
     { "bionj", 0, false }, { "nni", 0, true }, { "spr", 0, true }, { "upgma", 0, false }, { "wpgma", 0, false },
     { "site-coverage", 0, true }, { "complete-deletion", 0, false }, { "fit", 0, false }, { "fit-taxa", 0, true }, { "dump-newick", 0, true },
-    { "within", 0, true }, { "clusters", 0, true }, { "nearest", 0, true },
+    { "within", 0, true }, { "clusters", 0, true }, { "nearest", 0, true }, { "dendrogram", 0, true },
 };
 
 static void usageError(const std::string& what)
@@ -368,7 +386,7 @@ Options parseOptions(int argc, char** argv)
     auto treeBuilder = [&](const std::string& label, const char* wording, const char* noBootstrap, bool one_gpu) {
         if (o.algo == "1" || o.algo == "3") usageError(label + wording + " (-m 2, or the default mode below 30000 sequences)");
         if (o.add) usageError(label + " is not supported with --add");
-        if (params.out == "d" || params.out == "j" || params.out == "p" || params.out == "n") usageError(label + " needs tree output (-o t)");
+        if (params.out == "d" || params.out == "j" || params.out == "p" || params.out == "n" || params.out == "s") usageError(label + " needs tree output (-o t)");
         if (noBootstrap && has("bootstrap")) usageError(label + " is not supported with --bootstrap (" + noBootstrap + ")");
         if (o.njOnly.empty()) o.njOnly = label + wording;
         if (one_gpu) oneGpu.push_back(label);
@@ -469,6 +487,19 @@ Options parseOptions(int argc, char** argv)
         if (o.add || has("input-tree")) usageError("-o n is not supported with --add or -t (it compares the sequences of one input with each other)");
         if (has("bootstrap")) usageError("--bootstrap needs tree output (-o t)");
         oneGpu.push_back("-o n");
+    }
+    // -o s: the minimum spanning tree of the distances
+    o.mst = params.out == "s";
+    if (has("dendrogram") && !o.mst) usageError("--dendrogram needs the spanning-tree output (-o s)");
+    if (o.mst) {
+        if (o.add || has("input-tree")) usageError("-o s is not supported with --add or -t (it compares the sequences of one input with each other)");
+        if (has("bootstrap")) usageError("--bootstrap needs tree output (-o t)");
+        if (has("dendrogram")) {
+            o.dendrogramFile = vm.at("dendrogram");
+            if (o.dendrogramFile.empty()) usageError("--dendrogram: a file name");
+            if (o.dendrogramFile == o.outputFile) usageError("--dendrogram: the file must differ from the output file (-O)");
+        }
+        oneGpu.push_back("-o s");
     }
     parseBootstrap(vm, o);
 

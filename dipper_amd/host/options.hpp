@@ -25,6 +25,8 @@ struct Options {
     std::string withinText;      // ... and T as it was given (the reports name it so)
     bool nearest = false;        // -o n: the --nearest K nearest neighbours of every sequence
     int nearestK = 0;
+    bool mst = false;            // -o s: the minimum spanning tree of the distances and, with --dendrogram, the single-linkage tree
+    std::string dendrogramFile;
     std::string siteText;
     long long seed = 1;
     int device = 0;

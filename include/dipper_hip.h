@@ -897,6 +897,50 @@ int dpr_get_nearest_info(dpr_ctx *ctx, double ms[3], int64_t shape[2]);
  * takes it; j, d: n x K entries; cnt: n.  n < 2, K outside 1 .. 256, a null pointer: DPR_ERR_ARG, nothing written. */
 int dpr_nearest_host(const double *lower_rows, int64_t n, int K, int32_t *j, double *d, int32_t *cnt);
 
+/* ---- The minimum spanning forest of the distances (the command's -o s; no reference counterpart) -------------------------------------
+ * Contract.  Over the n tips of a source, with D_ij the entry dpr_dist_matrix would give the pair (read as a symmetric matrix): a pair
+ *   (i, j), i > j, is an edge candidate when D_ij is finite -- a NaN, +inf and -inf make no edge.  key(D) is the bits of D (of +0.0 for
+ *   either zero) with the sign bit flipped for D >= 0 and all bits flipped for D < 0, compared unsigned: the order of the finite
+ *   distances, negative ones included, -0.0 and +0.0 tying.  The candidates are totally ordered by (key(D_ij), i, j).  The answer is
+ *   the Kruskal forest under that strict order: a candidate is an edge exactly when its ends are not connected by smaller candidates.
+ *   It is unique: no tolerance, and nothing depends on block_rows, on a launch geometry or on the order in which wavefronts finish.
+ *   ei / ej / ed hold the E = n - C edges (C the number of components) ascending in that order, ei > ej, ed the entry bit for bit (a
+ *   -0.0 stays -0.0); label[v] is the smallest tip index of v's component, as dpr_pairs_labels gives it.  Cutting the edges at a
+ *   threshold T gives the components of dpr_pairs_* at T.
+ * dpr_mst_run takes the uploaded alignment (DPR_SRC_MSA, dist_type as dpr_dist_matrix takes it), the sketches (DPR_SRC_MASH, k the sketch
+ *   k) or the triangle of dpr_set_matrix_lower (DPR_SRC_MATRIX); DPR_ERR_STATE without that input.  ei, ej, ed: n - 1 places; label: n.
+ *   Fewer than two tips, a negative block_rows, a null pointer, several ranks, virtual ranks: DPR_ERR_ARG with nothing written.
+ *   block_rows: as dpr_nearest_begin takes it (at most 32 768 and n; 0 = the rows that put the block at 1 GiB or less, in whole multiples
+ *   of 64).  The full-row providers are relied on to give D_rc and D_cr the same bits, as dpr_nearest_* relies on them.
+ * Algorithm.  Boruvka over streamed blocks of full rows.  A round computes every block (the row provider; DPR_SRC_MATRIX: the expansion
+ *   of the triangle), finds per row the smallest (key, column) among the finite entries whose column lies in another component, takes
+ *   the minimum per component with integer atomics, emits every component's edge once, joins the components with the union-find of
+ *   dpr_pairs_* and tells the host how many edges there are: one synchronisation a round.  The rounds end when nothing was emitted or
+ *   one component is left; more than ceil(log2 n) + 1 rounds is DPR_ERR_STATE.  At the end the host sorts the edges and replays them
+ *   through a union-find: E != n - C, an edge between tips already joined or labels other than the device's is DPR_ERR_STATE (a source
+ *   that is not symmetric would show here); nothing is written then.
+ * Memory.  The n x n matrix is never allocated.  The device holds one block of FULL rows, 8 x block_rows x n bytes (n rounded up to 16
+ *   columns) and 56 bytes a tip (labels, row and component minima, the edges), all released before the call returns.
+ * State.  The context's inputs, its matrix and its NJ state are not touched; open streams of pairs or of neighbours are left alone.
+ * dpr_mst_stats, of the last successful dpr_mst_run (DPR_ERR_STATE before): out[0] rounds, 1 blocks computed, 2 edges, 3 components, 4
+ *   members of the largest, 5 components of one member, 6 the bytes of device memory the call held, 7 rows walked (rounds x n). */
+int dpr_mst_run(dpr_ctx *ctx, int source, int dist_type, int k, int64_t block_rows, int32_t *ei, int32_t *ej, double *ed, int64_t *edges,
+                int32_t *label);
+int dpr_mst_stats(dpr_ctx *ctx, int64_t out[8]);
+/* of the last dpr_mst_run (either may be NULL).  ms: summed over its rounds (HIP events) the row provider (DPR_SRC_MATRIX: the expansion
+ * of the triangle); the row minimum; the per-round component work (component minimum, emit) and the copy of the count.  shape: the rows
+ * of a block as the call settled them, n. */
+int dpr_get_mst_info(dpr_ctx *ctx, double ms[3], int64_t shape[2]);
+/* host only, no GPU: Kruskal -- every candidate sorted under the order, then a union-find -- on purpose not the device's algorithm; the
+ * reference of the GPU tests.  lower_rows: the strict lower triangle row by row, as dpr_set_matrix_lower takes it.  n < 2, a null
+ * pointer: DPR_ERR_ARG, nothing written. */
+int dpr_mst_host(const double *lower_rows, int64_t n, int32_t *ei, int32_t *ej, double *ed, int64_t *edges, int32_t *label);
+/* host only: the single-linkage dendrogram of a CONNECTED forest (edges == n - 1, in the contract's order; else DPR_ERR_ARG) as a merge
+ * log in the slot convention of dpr_upgma_run: merge t joins the components of edge t at height 0.5 * ed[t].  n - 1 entries each;
+ * dpr_tree_from_upgma and the command's UPGMA Newick writer take the log as it is. */
+int dpr_mst_dendrogram_host(int64_t n, const int32_t *ei, const int32_t *ej, const double *ed, int64_t edges, int32_t *merge_x,
+                            int32_t *merge_y, double *height);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
